@@ -16,16 +16,24 @@ A "step" is one pass of the hot path over one batch of synthetic live points.
                    been measured and the process exits non-zero.  The N = 1 line carries the one-GPU time of the
                    same 32768 rows (`strong_scaling_reference`).
 
-The N = 1 line also carries `other_configs` (B, E's 2048-row shard, E in full, D through host pointers: each both ways with the
-path taken and a parity spot check), `library_config` (the knobs the library ran under) and -- where this process sees several
-GPUs -- `multi_device_one_process`: config D through ONE context over 1 / 2 / 4 / all visible devices (mcalf_create_multi).
+A plain run sets up, runs W warm-up steps, times exactly K steps in one pass (`ms_per_step` = that pass / K) and prints
+the line; `library_config` (the knobs the library ran under) is in it.  Everything else is measured only with `--full`:
+the fused kernel alone (`kernel_ms`, the rooflines), the host-pointer passes, the other configurations, the CPU baselines
+and the parity spot checks against the oracle, and at N > 1 the ranks' kernel times and rank 0's split of a step.  With
+--full the N = 1 line also carries `other_configs` (B, E's 2048-row shard, E in full, D through host pointers: each both
+ways with the path taken and a parity spot check) and -- where this process sees several GPUs --
+`multi_device_one_process`: config D through ONE context over 1 / 2 / 4 / all visible devices (mcalf_create_multi).
 
 `value` is timed through the device-pointer entry, parameters resident in HBM when the timed region starts and
-logL left in HBM (the bench contract).  `value_host_api` is the same K steps through the host-pointer entry
+logL left in HBM (the bench contract).  With --full, `value_host_api` is the same K steps through the host-pointer entry
 `mcalf_loglike_batch` -- H2D of P and D2H of logL inside every step, SURVEY.md section 8(d)'s definition --
 measured in the same run and printed next to it.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+`--dump-outputs DIR` writes what the timed path returned in its last step -- the logL vector (rank 0: the gathered one at
+N > 1) -- as DIR/logL.npy in float64.  The inputs are drawn from the configuration's fixed seeds, so two builds run with
+the same arguments can be compared output for output.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -57,7 +65,8 @@ from mcalf_amd import dist as mdist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6   # MI355X vector FP64 peak
-MIN_PASS_MS = 50.0             # a timed pass shorter than this is repeated and the median pass reported
+MIN_PASS_MS = 50.0             # a timed pass shorter than this is repeated and the median pass reported (--full legs)
+MAX_DUMP_BYTES = 64_000_000    # --dump-outputs: a longer logL vector is written as every k-th row
 
 WORKLOAD_LABEL = {
     "A": "BASELINE config A: CIV 1548/1550, the reference's multicomponent mock spectrum (tests/golden)",
@@ -345,6 +354,11 @@ def main():
     ap.add_argument("--chunks", type=int, default=-1,
                     help="row blocks per batch inside the library (mcalf_set_chunks): -1 library default, 0 automatic, "
                          "1 = one fused launch per step (what the rocprofv3 summaries in profiles/ are taken with)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: kernel time and rooflines, host-pointer passes, the "
+                         "other configurations, CPU baselines and parity checks (the --no-* / --cpu-* options select among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the logL vector of the last timed step as DIR/logL.npy (float64)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline time budget (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the plain-C/OpenMP CPU baseline; 0 = every host core (os.cpu_count()), -1 = skip")
@@ -585,33 +599,40 @@ def main():
                 "step_ms_synchronous": float(seg.sum()), "how": how}
 
     def run_leg(kernels_ms_ref=None):
-        """Warm-up, timed passes, kernel pass, rank-0 split and gather check of the gather that is currently selected."""
+        """Warm-up, ONE timed pass of exactly --steps steps (seconds: the slowest rank's) and gather check of the gather that
+        is currently selected; with --full also the kernel pass and rank 0's split."""
         for _ in range(args.warmup):
             step()
-        el, passes = measure(step, args.steps, red_dev)
+        el = timed_pass(step, args.steps)
+        if use_dist:
+            t = torch.tensor([el], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            el = float(t.item())
         own = last_out[0].cpu().numpy().copy()
-        check = None
+        check = g = None
         if use_dist and rank == 0 and gathered[0] is not None:
             # the vector rank 0 holds after the last gather: its own block must be what it computed, and every
             # other block a finite logL of that rank's rows
-            g = gathered[0].cpu().numpy()
+            g = gathered[0].cpu().numpy().copy()
             check = {"rows": int(g.size), "own_block_equal": bool(np.array_equal(g[:batch], own)),
                      "all_finite": bool(np.isfinite(g).all())}
-        km = kernel_pass()
-        km = km if km is not None else el / args.steps * 1e3
-        kmin = kmax = km
-        if use_dist:                                     # load imbalance: the ranks' own kernel times
-            kt = torch.tensor([km, -km], dtype=torch.float64, device=red_dev)
-            dist.all_reduce(kt, op=dist.ReduceOp.MAX)
-            kmax, kmin = float(kt[0].item()), -float(kt[1].item())
         comm_ranks = None
         if inlib_box[0] is not None:                     # the LIBRARY's communicator says how many ranks it spans, not torch
             nr, rk = C.c_int32(0), C.c_int32(-1)
             _lib.check(fit._lib.mcalf_comm_info(fit._ctx, C.byref(nr), C.byref(rk)), fit._ctx)
             comm_ranks = int(nr.value)
-        return {"elapsed": el, "pass_times": passes, "logL": own, "gather_check": check, "kernel_ms": km,
-                "kernel_ms_min_over_ranks": kmin, "kernel_ms_max_over_ranks": kmax, "comm_ranks": comm_ranks,
-                "rank0_split": split_pass(kernels_ms_ref)}
+        leg = {"elapsed": el, "logL": own, "gathered": g, "gather_check": check, "comm_ranks": comm_ranks}
+        if args.full:
+            km = kernel_pass()
+            km = km if km is not None else el / args.steps * 1e3
+            kmin = kmax = km
+            if use_dist:                                 # load imbalance: the ranks' own kernel times
+                kt = torch.tensor([km, -km], dtype=torch.float64, device=red_dev)
+                dist.all_reduce(kt, op=dist.ReduceOp.MAX)
+                kmax, kmin = float(kt[0].item()), -float(kt[1].item())
+            leg.update({"kernel_ms": km, "kernel_ms_min_over_ranks": kmin, "kernel_ms_max_over_ranks": kmax,
+                        "rank0_split": split_pass(kernels_ms_ref)})
+        return leg
 
     GATHER_WHAT = {
         "torch": "torch.distributed.gather, two buffers in flight",
@@ -658,14 +679,14 @@ def main():
             watchdog = threading.Timer(args.leg_timeout, emit_partial_and_exit, args=(name,))
             watchdog.daemon = True
             watchdog.start()
-        ref = legs["torch"]["rank0_split"]["kernels_ms"] if ("torch" in legs and legs["torch"]["rank0_split"]) else None
-        legs[name] = run_leg(ref)
+        split = legs["torch"].get("rank0_split") if "torch" in legs else None
+        legs[name] = run_leg(split["kernels_ms"] if split else None)
         if watchdog is not None:
             watchdog.cancel()
     reported = min(legs, key=lambda k: legs[k]["elapsed"])
     inlib_box[0] = None                                  # (what follows fences through the torch plan again)
-    elapsed, pass_times = legs[reported]["elapsed"], legs[reported]["pass_times"]
-    logL_dev, gather_check, kern_ms = legs[reported]["logL"], legs[reported]["gather_check"], legs[reported]["kernel_ms"]
+    elapsed = legs[reported]["elapsed"]
+    logL_dev, gather_check, kern_ms = legs[reported]["logL"], legs[reported]["gather_check"], legs[reported].get("kernel_ms")
     tot = torch.tensor([comp_pix, line_pix], dtype=torch.float64, device=red_dev)
     if use_dist:
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
@@ -674,7 +695,7 @@ def main():
     # PCIe-inclusive passes through the host-pointer entry (N = 1): pageable numpy arrays as a sampler holds
     # them, then page-locked ones
     host_api = None
-    if world == 1 and not args.no_host_api:
+    if args.full and world == 1 and not args.no_host_api:
         out_host = np.empty(batch)
         fit.loglike_batch(P_host, out=out_host)
         t_host, _ = measure(lambda: fit.loglike_batch(P_host, out=out_host), args.steps, red_dev, min_passes=3)
@@ -725,7 +746,7 @@ def main():
 
     # N = 1 leg of the strong-scaling job: config D's 32768 rows on this one GPU
     strong_ref = None
-    if world == 1 and config == "C" and not args.no_strong_ref and not args.batch:
+    if args.full and world == 1 and config == "C" and not args.no_strong_ref and not args.batch:
         kwD, batchD, seedD = workloads.config("D", hip_synth)
         PD = workloads.draw_P(kwD, batchD, np.random.default_rng(seedD))
         dPD = torch.from_numpy(PD).to(dev)
@@ -757,7 +778,7 @@ def main():
     # Model-output entry (reconstruct_spec for the whole batch, hires_fitter.py:409-449; consumer cli.py:414-418):
     # the only mode in which HBM bytes matter -- 8 * npix B per live point are written
     model_leg = None
-    if world == 1 and not args.no_model_leg and not extra:
+    if args.full and world == 1 and not args.no_model_leg and not extra:
         dflux = torch.empty((batch, npix), dtype=torch.float64, device=dev)
         model_fn = fit._lib.mcalf_model_batch_device
 
@@ -794,7 +815,7 @@ def main():
     # clock: B, E's per-GPU shard at N = 8 (2048 rows) and E in full (16384 rows).  (D through host pointers: the
     # strong-scaling reference above carries it.)
     other = None
-    if world == 1 and config == "C" and not args.no_other_configs and not args.batch and not extra:
+    if args.full and world == 1 and config == "C" and not args.no_other_configs and not args.batch and not extra:
         other = {"B": config_leg("B", None, steps=max(20, args.steps), device=local_rank),
                  "E_shard_2048": config_leg("E", 2048, steps=max(10, args.steps // 2), device=local_rank),
                  "E_full_16384": config_leg("E", None, steps=max(5, args.steps // 5), device=local_rank)}
@@ -802,13 +823,6 @@ def main():
     out = None
     if rank == 0:
         n_half = fit.info.n_cap
-        alg_bytes = (8 * ndim + 8) * batch + 24 * npix
-        alg_flops = 40.0 * line_pix + (31 + 4 * n_half) * npix * batch
-        ach_gbs = alg_bytes / (kern_ms * 1e-3) / 1e9
-        std_batch = not args.batch and (world == 1 or scaling == "strong")
-        lib_hash = library_source_hash(fit._lib)
-        tr, tr_note = stamped(load_profile_json("traffic.json", config) if std_batch and world == 1 else None, lib_hash)
-        pmc, pmc_note = stamped(load_profile_json("pmc.json", config) if std_batch and world == 1 else None, lib_hash)
         ms_per_step = elapsed / args.steps * 1e3
         out = {
             "metric": "component-pixel Voigt evals/s (sum_s ncomp_s * npix / t), logL batch on MI355X: `value` with the inputs "
@@ -818,7 +832,7 @@ def main():
                                 "HBM when the timed region starts; a PCIe-inclusive rate is reported beside it and is never "
                                 "`value`.  SURVEY.md 8(d) defines the step with H2D of P and D2H of logL inside: that figure is "
                                 "`value_host_api` / `ms_per_step_host_api` (pageable numpy arrays, one synchronous call per "
-                                "step), timed in the same run; `host_api.host_over_device` is their ratio",
+                                "step), timed in the same run with --full; `host_api.host_over_device` is their ratio",
             "value": comp_pix_job * args.steps / elapsed,
             "unit": "evals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -826,8 +840,8 @@ def main():
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "entry": "device pointers (P resident in HBM, logL left in HBM)",
-            "timing": {"passes": len(pass_times), "steps_per_pass": args.steps, "reported": "median pass",
-                       "pass_ms": [round(t * 1e3, 4) for t in pass_times]},
+            "timing": {"passes": 1, "steps_per_pass": args.steps, "reported": "one pass of exactly `steps` steps",
+                       "pass_ms": [round(elapsed * 1e3, 4)]},
             "batches_in_flight": max(1, args.inflight if world == 1 else 1),
             "config": {"workload": WORKLOAD_LABEL[config], "batch_per_gpu": batch, "global_batch": batch * world,
                        "npix": npix, "ncomp": list(kw["ncomp"]), "nlines": nlines, "nfill": fit.nfill, "ndim": ndim,
@@ -838,35 +852,44 @@ def main():
                                        if world > 1 else "single GPU")},
             "logL_per_s": batch * world * args.steps / elapsed,
             "line_pixel_evals_per_s": line_pix_job * args.steps / elapsed,
-            "kernel_ms": kern_ms,
-            "roofline": {"bound": "hbm", "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach_gbs / HBM_PEAK_GBS, "traffic": tr["traffic_bytes_per_launch"] if tr else None,
-                         "traffic_note": tr_note,
-                         "kernel": "mcalf_fused_kernel (one launch over the whole batch)",
-                         "kernel_source_hash": lib_hash,
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "note": "the fused path is FP64-VALU bound, not HBM bound (arithmetic intensity > 1e3 FLOP/B, "
-                                 "SURVEY.md 8d): the HBM fraction is ~1e-3 by construction; see roofline_valu"},
-            "roofline_valu": {"bound": "fp64_valu", "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                              "throughput_equivalent": alg_flops / (kern_ms * 1e-3) / 1e12,
-                              "throughput_equivalent_frac": alg_flops / (kern_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
-                              "algorithmic_flops_per_launch": alg_flops,
-                              "note": "throughput_equivalent prices SURVEY 8(d)'s nominal 40 FLOP per line-pixel; the "
-                                      "far-wing interpolation legitimately skips most of those evaluations, so it is "
-                                      "NOT a bound (it exceeds 1 at config E) and not pipe utilisation: `achieved` / "
-                                      "`frac` are the FP64 operations the pipes executed (PMC instruction mix), "
-                                      "valu_busy the share of cycles the vector pipe was issuing",
-                              "pmc_note": pmc_note},
         }
-        if pmc:
-            out["roofline_valu"].update({k: pmc[k] for k in ("valu_busy", "executed_flops_per_launch", "executed_flops_note",
-                                                             "valu_active_lane_fraction", "valu_active_lane_fraction_note", "executed_flops_lane_weighted_estimate",
-                                                             "source") if k in pmc})
-            if "executed_flops_per_launch" in pmc:
-                ex = pmc["executed_flops_per_launch"] / (kern_ms * 1e-3) / 1e12
-                out["roofline_valu"].update({"achieved": ex, "frac": ex / FP64_VALU_PEAK_TFLOPS})
-            if "issue" in pmc:
-                out["roofline_issue"] = issue_model(pmc["issue"], kern_ms)
+        if args.full:
+            alg_bytes = (8 * ndim + 8) * batch + 24 * npix
+            alg_flops = 40.0 * line_pix + (31 + 4 * n_half) * npix * batch
+            ach_gbs = alg_bytes / (kern_ms * 1e-3) / 1e9
+            std_batch = not args.batch and (world == 1 or scaling == "strong")
+            lib_hash = library_source_hash(fit._lib)
+            tr, tr_note = stamped(load_profile_json("traffic.json", config) if std_batch and world == 1 else None, lib_hash)
+            pmc, pmc_note = stamped(load_profile_json("pmc.json", config) if std_batch and world == 1 else None, lib_hash)
+            out.update({
+                "kernel_ms": kern_ms,
+                "roofline": {"bound": "hbm", "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": ach_gbs / HBM_PEAK_GBS, "traffic": tr["traffic_bytes_per_launch"] if tr else None,
+                             "traffic_note": tr_note,
+                             "kernel": "mcalf_fused_kernel (one launch over the whole batch)",
+                             "kernel_source_hash": lib_hash,
+                             "algorithmic_bytes_per_launch": alg_bytes,
+                             "note": "the fused path is FP64-VALU bound, not HBM bound (arithmetic intensity > 1e3 FLOP/B, "
+                                     "SURVEY.md 8d): the HBM fraction is ~1e-3 by construction; see roofline_valu"},
+                "roofline_valu": {"bound": "fp64_valu", "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                  "throughput_equivalent": alg_flops / (kern_ms * 1e-3) / 1e12,
+                                  "throughput_equivalent_frac": alg_flops / (kern_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TFLOPS,
+                                  "algorithmic_flops_per_launch": alg_flops,
+                                  "note": "throughput_equivalent prices SURVEY 8(d)'s nominal 40 FLOP per line-pixel; the "
+                                          "far-wing interpolation legitimately skips most of those evaluations, so it is "
+                                          "NOT a bound (it exceeds 1 at config E) and not pipe utilisation: `achieved` / "
+                                          "`frac` are the FP64 operations the pipes executed (PMC instruction mix), "
+                                          "valu_busy the share of cycles the vector pipe was issuing",
+                                  "pmc_note": pmc_note}})
+            if pmc:
+                out["roofline_valu"].update({k: pmc[k] for k in ("valu_busy", "executed_flops_per_launch", "executed_flops_note",
+                                                                 "valu_active_lane_fraction", "valu_active_lane_fraction_note", "executed_flops_lane_weighted_estimate",
+                                                                 "source") if k in pmc})
+                if "executed_flops_per_launch" in pmc:
+                    ex = pmc["executed_flops_per_launch"] / (kern_ms * 1e-3) / 1e12
+                    out["roofline_valu"].update({"achieved": ex, "frac": ex / FP64_VALU_PEAK_TFLOPS})
+                if "issue" in pmc:
+                    out["roofline_issue"] = issue_model(pmc["issue"], kern_ms)
         # (the same two figures under explicit names, whichever convention a reader expects for `value`)
         out["value_device_resident"], out["ms_per_step_device_resident"] = out["value"], ms_per_step
         if host_api:
@@ -891,7 +914,7 @@ def main():
                                    "bit_equal_host_vs_device_entry": strong_ref["host_api"]["bit_equal_to_device_entry"]}
             out["other_configs"] = other
         out["library_config"] = fit.get_config()
-        if world == 1 and config == "C" and not args.no_multi_device and not args.batch:
+        if args.full and world == 1 and config == "C" and not args.no_multi_device and not args.batch:
             md = run_multi_device_leg()
             # (None on a one-GPU lease; on a node whose GPUs this process all sees: ONE process driving them)
             out["multi_device_one_process"] = md if md is not None else "skipped: this process sees one GPU"
@@ -911,20 +934,18 @@ def main():
                     out["gathers"][name] = {
                         "what": GATHER_WHAT[name], "ms_per_step": lg["elapsed"] / args.steps * 1e3,
                         "value": comp_pix_job * args.steps / lg["elapsed"], "gather_check": lg["gather_check"],
-                        "kernel_ms_min_over_ranks": lg["kernel_ms_min_over_ranks"],
-                        "kernel_ms_max_over_ranks": lg["kernel_ms_max_over_ranks"],
-                        "rank0_split": lg["rank0_split"],
                         # who says how many ranks took part: torch's process group for its gather, the library's own
                         # communicator (mcalf_comm_info) for the library's legs
                         "rccl_ranks": lg["comm_ranks"] if lg["comm_ranks"] is not None else rccl_ranks,
-                        "rccl_ranks_source": "mcalf_comm_info" if lg["comm_ranks"] is not None else "torch.distributed.get_world_size",
-                        "passes": len(lg["pass_times"])}
+                        "rccl_ranks_source": "mcalf_comm_info" if lg["comm_ranks"] is not None else "torch.distributed.get_world_size"}
+                    out["gathers"][name].update({k: lg[k] for k in ("kernel_ms_min_over_ranks", "kernel_ms_max_over_ranks",
+                                                                    "rank0_split") if k in lg})
                 else:
                     out["gathers"][name] = leg_notes.get(name, "not run")
             if rehearsal:
                 out["gathers_note"] = ("gloo REHEARSAL on one GPU: every rank shares cuda:0; the library legs run over the tests' "
                                        "stand-in transport when MCALF_RCCL_LIB names it, else they are skipped")
-        if args.cpu_seconds > 0 and world == 1:          # the CPU baseline is an N=1 figure (rank 0 only)
+        if args.full and args.cpu_seconds > 0 and world == 1:    # the CPU baseline is an N=1 figure (rank 0 only)
             vals, dt, done = cpu_baseline(kw, P_host, args.cpu_seconds)
             k = len(vals)
             evals = sum(float(nc[i % batch]) for i in range(done)) * npix
@@ -961,12 +982,19 @@ def main():
                 if len(runs) > 1:
                     best["other_thread_counts"] = [{"cores": r["cores"], "value": r["value"]} for r in runs if r is not best]
                 out["cpu_baseline_c_openmp"] = best
-    if out is not None and world > 1 and args.cpu_seconds > 0:
+    if args.full and out is not None and world > 1 and args.cpu_seconds > 0:
         # N>1: no CPU timing, only a parity spot check of rank 0's first rows against the oracle
         vals, _, _ = cpu_baseline(kw, P_host[:8], 0.0)
         out["parity"] = {"max_abs_dlogL_vs_oracle": float(np.abs(vals - logL_dev[:len(vals)]).max()), "rows": len(vals)}
     if out is not None and gather_check is not None:
         out["gather_check"] = gather_check
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path holds after the last timed step: rank 0's gathered vector at N > 1
+        logl = legs[reported]["gathered"] if legs[reported]["gathered"] is not None else logL_dev
+        logl = np.ascontiguousarray(logl, dtype=np.float64)
+        stride = max(1, -(-logl.nbytes // MAX_DUMP_BYTES))     # 1 unless the vector is longer than the cap allows
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logL.npy"), logl[::stride])
     fit.close()
     for f2, _, _ in extra:
         f2.close()

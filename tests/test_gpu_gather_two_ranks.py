@@ -141,7 +141,7 @@ def test_bench_n2_times_the_three_gathers_in_one_process_group(fake_rccl):
     """`bench.py --gpus 2` (gloo rehearsal on the one GPU, the library's exchange over the stand-in transport): the torch
     gather, the library's exchange on the launch stream and the library's exchange on its side stream are timed one after
     the other in the ONE process group, each with its gather check and the ranks' kernel times; the best is `value`."""
-    res, out = _bench_two_ranks(fake_rccl)
+    res, out = _bench_two_ranks(fake_rccl, "--full")
     assert res.returncode == 0, res.stderr[-2000:]
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and list(out["gathers"]) == ["torch", "inlib", "inlib_overlap"]
     for name, g in out["gathers"].items():

@@ -174,7 +174,7 @@ def test_two_rank_job_through_the_product_path_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", "D",
-           "--batch", "2048", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"]
+           "--batch", "2048", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]

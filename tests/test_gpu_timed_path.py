@@ -452,3 +452,30 @@ def test_set_up_geometry_and_chunked_ordering_do_not_change_results(block, monke
         assert fit.last_launch().persistent == 0 and fit.last_launch().inline_setup == 0
     assert np.array_equal(got, ref) and np.array_equal(small, ref[:700])
 
+
+
+def test_plain_bench_run_times_exactly_steps_and_dumps_the_timed_output(tmp_path):
+    """`bench.py` without --full: ONE timed pass of exactly --steps steps, nothing beyond the headline in the line, and
+    --dump-outputs writes the logL vector of the last timed step -- the device entry's bits for the seeded inputs."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "B", "--steps", "7",
+                        "--warmup", "2", "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["timing"]["passes"] == 1
+    assert out["timing"]["pass_ms"][0] == pytest.approx(7 * out["ms_per_step"], abs=1e-3)
+    assert not {"kernel_ms", "roofline", "host_api", "strong_scaling_reference", "model_output", "cpu_baseline",
+                "parity"} & set(out)
+    kw, batch, seed = workloads.config("B", bench.hip_synth)
+    P = workloads.draw_P(kw, batch, np.random.default_rng(seed))
+    with mcalf_amd.als_fitter(None, **kw) as fit:
+        _lib.check(fit._lib.mcalf_reserve(fit._ctx, batch), fit._ctx)
+        want = _device_logl(fit, torch.from_numpy(P).cuda(), batch)
+        comp_pix = float(P[:, fit.startind].astype(int).sum()) * fit.obj_wl.size
+    got = np.load(tmp_path / "dump" / "logL.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, want)
+    assert out["value"] == pytest.approx(comp_pix / (out["ms_per_step"] * 1e-3))

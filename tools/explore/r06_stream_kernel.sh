@@ -7,7 +7,7 @@ for rep in 1 2; do
   for cfg in C D E; do
     for v in 0 1; do
       steps=100; [ $cfg = E ] && steps=20; [ $cfg = D ] && steps=20
-      MCALF_STREAM_DEVICE=$v timeout -k 10 300 python3 bench.py --config $cfg --gpus 1 --steps $steps --cpu-seconds 0 --no-host-api --no-strong-ref --no-model-leg --no-other-configs 2>/dev/null | python3 -c "
+      MCALF_STREAM_DEVICE=$v timeout -k 10 300 python3 bench.py --full --config $cfg --gpus 1 --steps $steps --cpu-seconds 0 --no-host-api --no-strong-ref --no-model-leg --no-other-configs 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$cfg stream_device=$v ms_per_step %.4f kernel_ms %.4f' % (d['ms_per_step'], d['kernel_ms']))" >> $out/stream_kernel.txt
     done
   done

@@ -7,8 +7,8 @@
 cfg=${1:-C}; out=${2:-gpurun_out/prof_$cfg}; steps=${3:-50}; tag=${4:-r06}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$out"
-timeout -k 10 600 python bench.py --config $cfg --steps $steps > "$out/bench.json" 2> "$out/bench.err" || echo "bench failed"
-common="--config $cfg --steps $steps --warmup 5 --cpu-seconds 0 --no-host-api --no-strong-ref --no-model-leg --no-other-configs --no-multi-device"
+timeout -k 10 600 python bench.py --full --config $cfg --steps $steps > "$out/bench.json" 2> "$out/bench.err" || echo "bench failed"
+common="--full --config $cfg --steps $steps --warmup 5 --cpu-seconds 0 --no-host-api --no-strong-ref --no-model-leg --no-other-configs --no-multi-device"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/ktrace" --output-format csv -- python3 bench.py $common > "$out/ktrace_bench.json" 2> "$out/ktrace.err" || echo "kernel trace failed"
 find "$out/ktrace" -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} "$out/kernel_stats.csv"
 i=0
@@ -28,6 +28,6 @@ done
   && python3 tools/micro/lane_unit_summary.py "$out/lane_unit" "$out/lane_unit.json" > "$out/lane_unit.txt"
 python3 tools/profiles_summary.py "$cfg" "$out"
 python3 tools/collect_profiles.py --round $tag --src "$out" $cfg
-timeout -k 10 600 python bench.py --config $cfg --steps $steps > "$out/bench_with_counters.json" 2> "$out/bench_with_counters.err" || echo "second bench failed"
+timeout -k 10 600 python bench.py --full --config $cfg --steps $steps > "$out/bench_with_counters.json" 2> "$out/bench_with_counters.err" || echo "second bench failed"
 cp "$out/bench_with_counters.json" profiles/${tag}_bench_${cfg}_with_counters.json
 mkdir -p gpurun_out/profiles_${tag}; cp profiles/${tag}_* profiles/pmc.json profiles/traffic.json gpurun_out/profiles_${tag}/ 2>/dev/null
