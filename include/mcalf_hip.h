@@ -18,6 +18,8 @@
  *   mcalf_chi2_batch       <- als_fitter.chi2                         hires_fitter.py:236-248
  *   mcalf_scale_cube_batch <- _scale_cube_pc / _scale_cube_mn         hires_fitter.py:202-216
  *   mcalf_loglike_cube_batch <- lnlhood_pc(_scale_cube_pc(cube))      hires_fitter.py:202-209,250-262
+ *   mcalf_loglike_grad_batch <- jax.grad of the get_jax_likelihood closure  hires_fitter.py:521-695
+ *                             (no counterpart on the numpy path: finite differences of lnlhood_worker)
  *   mcalf_voigt_hjerting[_nodes] <- scipy.special.wofz(u + i a).real  hires_fitter.py:365
  *                             / voigt_jax.hjert                       voigt_jax.py:121-127
  *   mcalf_set_cu_mask, mcalf_stream_partition
@@ -61,7 +63,7 @@
 extern "C" {
 #endif
 
-#define MCALF_ABI_VERSION 7   /* 2: mcalf_last_launch, gatherv / overlap / join, version string carries the source hash
+#define MCALF_ABI_VERSION 8   /* 2: mcalf_last_launch, gatherv / overlap / join, version string carries the source hash
                                  3: MCALF_PATH_HOST_STREAM, mcalf_launch_info_t grows by stream_setup_wgs / stream_polled
                                  4: mcalf_broker_serve
                                  5: mcalf_set_resident, mcalf_broker_serve_resident
@@ -69,7 +71,8 @@ extern "C" {
                                     stream_wgs_max / stream_fallback (the streaming launch is taken only on the device shape it
                                     was built for, and checked after every launch)
                                  7: mcalf_create_multi, mcalf_last_launch_sub, mcalf_get_config; mcalf_info_t grows by ndevices /
-                                    devices[16], mcalf_launch_info_t by devices_used */
+                                    devices[16], mcalf_launch_info_t by devices_used
+                                 8: mcalf_loglike_grad_batch[_device], mcalf_voigt_hjerting_grad (the analytic gradient of logL) */
 
 enum {
     MCALF_OK = 0,
@@ -297,6 +300,20 @@ int mcalf_loglike_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, 
 int mcalf_model_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t targonly,
                              double* dflux, void* stream);
 
+/* The analytic gradient of logL: logL[i] as mcalf_loglike_batch gives it and G[i, k] = d logL[i] / d P[i, k]
+ * (batch x ndim, row-major) under the context's conv_mode.  Columns that are 0 by definition: the ncomp slot and
+ * the (N, z, b) of every component at or beyond the row's active count.  Rows whose logL is -inf (asymmetric veto)
+ * or NaN get an all-NaN row of G.  On the numpy path the LSF tap count is held at its value for the row: G is the
+ * derivative within that piece (logL itself jumps where the count changes); the R column is 0 when R <= velstep.
+ * Host pointers, synchronous; `logL` may be NULL.  A multi-device context cuts the batch into contiguous row
+ * blocks, one per device, written straight into the caller's arrays.  A row's result does not depend on its
+ * batch, its position or the device count (every reduction runs in a fixed order). */
+int mcalf_loglike_grad_batch(mcalf_ctx* ctx, const double* P, int64_t batch, double* logL, double* G);
+/* Same, device pointers, on the caller's stream (single-device contexts).  After one call of the same or a larger
+ * batch it allocates and synchronises nothing. */
+int mcalf_loglike_grad_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG,
+                                    void* stream);
+
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel
  * launch of that call. */
@@ -438,6 +455,9 @@ int mcalf_voigt_hjerting(const double* x, const double* y, int64_t n, double* ou
 /* Same with the arithmetic an interpolation NODE gets: between x_c (6.2 for K = 1) and 8 the zone-1 wing
  * polynomial with exp(-x^2) dropped, instead of the core table a directly evaluated pixel uses there. */
 int mcalf_voigt_hjerting_nodes(const double* x, const double* y, int64_t n, double* out, int32_t device);
+/* The gradient path's Voigt function and its partials: out[3i], out[3i+1], out[3i+2] = H, dH/dx, dH/dy at
+ * (x[i], y[i]), y >= 0 (host pointers; device = -1 for the current device). */
+int mcalf_voigt_hjerting_grad(const double* x, const double* y, int64_t n, double* out, int32_t device);
 
 #ifdef __cplusplus
 }

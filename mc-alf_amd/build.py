@@ -1,8 +1,10 @@
 """Build libmcalf_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is seven translation units: kernels.hip (every kernel: the only file compiled for the device) and the host
-side of the C ABI -- host_abi.cpp, host_stream.cpp, host_config.cpp, host_multi.cpp, broker.cpp, comm.cpp -- compiled as plain C++ against the HIP
-runtime API.  Objects are kept under csrc/obj/ so that an edit of a host file does not recompile the kernels (22 s)."""
+The library is nine translation units: two device files -- kernels.hip (the likelihood's kernels) and grad_kernels.hip
+(the analytic gradient's) -- and the host side of the C ABI -- host_abi.cpp, host_stream.cpp, host_config.cpp,
+host_multi.cpp, host_grad.cpp, broker.cpp, comm.cpp -- compiled as plain C++ against the HIP runtime API.  Objects are
+kept under csrc/obj/ so that an edit of a host file does not recompile the kernels (22 s), and an edit of the gradient's
+device files does not recompile the likelihood's."""
 from __future__ import annotations
 
 import hashlib
@@ -12,11 +14,15 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 KERNEL_SOURCE = "kernels.hip"
-HOST_SOURCES = ["host_abi.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "broker.cpp", "comm.cpp"]
-SOURCES = [KERNEL_SOURCE] + HOST_SOURCES
+GRAD_SOURCE = "grad_kernels.hip"
+DEVICE_SOURCES = [KERNEL_SOURCE, GRAD_SOURCE]
+HOST_SOURCES = ["host_abi.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "host_grad.cpp", "broker.cpp", "comm.cpp"]
+SOURCES = DEVICE_SOURCES + HOST_SOURCES
 # what the DEVICE code is made of: the kernel-source hash covers exactly these
 HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h"]
-HOST_HEADERS = ["host_ctx.h", "kernel_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
+# the gradient's device object (not hashed: the fused kernel does not include these)
+GRAD_DEPS = ["grad_kernels.hip", "grad_args.h", "voigt_grad.h", "kernel_args.h", "voigt_tables.h"]
+HOST_HEADERS = ["host_ctx.h", "kernel_args.h", "grad_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
 TARGET = os.path.join(CSRC, "libmcalf_hip.so")
 OBJDIR = os.path.join(CSRC, "obj")
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
@@ -33,7 +39,9 @@ def _mtime(name: str) -> float:
 
 
 def _deps(src: str):
-    return [src] + (HASHED if src == KERNEL_SOURCE else HOST_HEADERS)
+    if src == KERNEL_SOURCE:
+        return [src] + HASHED
+    return GRAD_DEPS if src == GRAD_SOURCE else [src] + HOST_HEADERS
 
 
 def _stale(target: str, deps) -> bool:
@@ -92,6 +100,12 @@ def build(force: bool = False, verbose: bool = False, testing: bool = False, tar
             fh.write(stamp)
         relinked = True
     objs.append(kobj)
+    # the gradient's kernel object (also shared by both variants)
+    gobj = os.path.join(OBJDIR, "grad_kernels.o")
+    if (force and not testing) or _stale(gobj, _deps(GRAD_SOURCE)):
+        _run([hipcc] + KERNEL_FLAGS + ["-c", GRAD_SOURCE, "-o", gobj], verbose)
+        relinked = True
+    objs.append(gobj)
     for src in HOST_SOURCES:
         obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         # (host_abi.cpp carries the hash string: it is recompiled when the kernels changed)
@@ -115,6 +129,8 @@ def build_tree(workdir: str, target: str, stamp: str = "patched-copy", defines=(
         obj = os.path.splitext(src)[0] + ".o"
         if src == KERNEL_SOURCE:
             cmd = [hipcc] + KERNEL_FLAGS + list(kernel_flags) + (["-Rpass-analysis=kernel-resource-usage"] if report else [])
+        elif src in DEVICE_SOURCES:
+            cmd = [hipcc] + KERNEL_FLAGS
         else:
             cmd = [hipcc] + HOST_FLAGS + [f'-DMCALF_SRC_HASH="{stamp}"']
         res = subprocess.run(cmd + [f"-D{d}" for d in defines] + ["-c", src, "-o", obj], cwd=workdir, capture_output=True, text=True)

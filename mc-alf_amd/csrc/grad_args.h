@@ -1,0 +1,41 @@
+// What the gradient kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
+// workspace layout and the kernel entry points.  Plain C++ -- host_grad.cpp is compiled without the HIP language mode.
+// Not part of the kernel-source hash (mc-alf_amd/build.py): the fused kernel does not include it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "kernel_args.h"
+
+namespace mcalf {
+
+constexpr int kGradBlock = 256;          // threads per workgroup; one pixel per thread, so also the tile of the pixel kernels
+constexpr int kGradRec = 6;              // doubles per (component, line) record: A, B, a, K, 1/dnu, 1/b
+constexpr int kGradRow = 8;              // doubles per row: R, cont, half-width n, active components, bad flag, bot, (pad)
+constexpr size_t kGradChunkBytes = size_t(384) << 20;   // per-row workspaces of one pass (F, q, taps, ...) at most this big
+
+// One pass over `nrows` rows of a batch (rows [row0, row0 + nrows) of the caller's arrays).
+struct GradArgs {
+    const double* P;          // parameter rows of this pass, row-major [nrows, ndim]
+    const double* logL;       // their logL (the fused kernel's): -inf / NaN rows get an all-NaN gradient
+    double* G;                // gradient rows of this pass [nrows, ndim]
+    const double *nu, *obj, *ispec2, *lgis;
+    const LineDev* lines;     // nlines target lines, then the filler line
+    double *rows, *recs, *taps, *dtaps;      // per-row workspaces: [nrows, kGradRow], [nrows, nslots, kGradRec], [nrows, tapcap] x 2
+    double *F, *q;            // [nrows, npix]: transmitted flux (then g = -F cont L^T q), weighted residual
+    double* part;             // [nrows, ntiles, ndim] per-tile partial sums of the gradient
+    int nrows, npix, ndim, ntiles, tapcap, nslots;
+    int nlines, ncompmax, nfill, startind, endind, freespecres, freecont, jax, jax_half, n_cap;
+    double specres_fixed, contval_fixed, velstep;
+};
+
+// grad_kernels.hip; every kernel takes (const GradArgs a), grid as stated
+MCALF_INTERNAL const void* grad_setup_kernel_ptr();      // grid = nrows: decode, records, taps
+MCALF_INTERNAL const void* grad_forward_kernel_ptr();    // grid = (ntiles, nrows): F = exp(-tau)
+MCALF_INTERNAL const void* grad_model_kernel_ptr();      // grid = (ntiles, nrows): q, continuum and R partials
+MCALF_INTERNAL const void* grad_adjoint_kernel_ptr();    // grid = (ntiles, nrows): g = -F cont L^T q (in place of F)
+MCALF_INTERNAL const void* grad_deriv_kernel_ptr();      // grid = (ntiles, nrows): (N, z, b) partials
+MCALF_INTERNAL const void* grad_finalize_kernel_ptr();   // grid = ceil(nrows * ndim / kGradBlock): tiles summed in order
+MCALF_INTERNAL const void* grad_hjert_kernel_ptr();      // (const double* x, const double* y, long n, double* out): out[3i..] = H, H_x, H_y
+
+}  // namespace mcalf

@@ -22,7 +22,7 @@ int set_err(mcalf_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-static int pick_device(mcalf_ctx* ctx, int requested, int* out_dev, std::string* arch) {
+int pick_device(mcalf_ctx* ctx, int requested, int* out_dev, std::string* arch) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0)
@@ -71,6 +71,7 @@ extern "C" void mcalf_destroy(mcalf_ctx* ctx) {
     ctx->stagers.clear();
     (void)hipSetDevice(ctx->device);
     comm_release(ctx);
+    grad_release(ctx);
     resident_stop(ctx);
     if (ctx->res_stream) (void)hipStreamDestroy(ctx->res_stream);
     if (ctx->h_box) (void)hipHostFree((void*)ctx->h_box);

@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_stream.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_stream.cpp, host_grad.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -262,6 +262,12 @@ struct mcalf_ctx {
     SampleHdr* d_whdr = nullptr;
     size_t cap_wide = 0, cap_wtaps = 0, cap_wpartial = 0, cap_wrows = 0, cap_whdr = 0;
     mcalf_launch_info_t last = {};      // what the last call did (mcalf_last_launch)
+    // Gradient entries (host_grad.cpp): per-row workspaces of one pass, F / q of its rows, per-tile partials, and the
+    // parameter / logL / gradient rows of the host-pointer entry (all grown on demand)
+    double *g_rows = nullptr, *g_recs = nullptr, *g_taps = nullptr, *g_dtaps = nullptr, *g_F = nullptr, *g_q = nullptr, *g_part = nullptr;
+    double *g_P = nullptr, *g_logL = nullptr, *g_G = nullptr;
+    size_t cap_g_rows = 0, cap_g_recs = 0, cap_g_taps = 0, cap_g_dtaps = 0, cap_g_F = 0, cap_g_q = 0, cap_g_part = 0;
+    size_t cap_g_P = 0, cap_g_logL = 0, cap_g_G = 0;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -312,6 +318,7 @@ int launch(mcalf_ctx* ctx, int mode, const double* dP, int64_t batch, int targon
 int launch_preflight(mcalf_ctx* ctx, int mode, int64_t batch);
 int launch_finalize(mcalf_ctx* ctx, const KArgs& a, int64_t nrows, int mode, hipStream_t stream, int nparts = 0, bool signal = false);
 int ensure_small(mcalf_ctx* ctx);                      // the page-locked block of small calls
+int pick_device(mcalf_ctx* ctx, int requested, int* out_dev, std::string* arch);   // a usable gfx950 device (-1: the current one)
 bool is_pinned_host(const void* p);
 // A stream of the context: created with the context's CU mask when it has one (mcalf_set_cu_mask).
 int create_stream(mcalf_ctx* ctx, hipStream_t* out, int priority = 0);
@@ -355,6 +362,9 @@ void host_trace_report(mcalf_ctx* ctx);          // host_abi.cpp: MCALF_HOST_TRA
 void resident_stop(mcalf_ctx* ctx);
 bool resident_serves(const mcalf_ctx* ctx, int mode, int64_t batch, int rowlen, bool from_cube);
 int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out);
+
+// ---- host_grad.cpp: the analytic gradient of logL ------------------------------------------------------------------------
+void grad_release(mcalf_ctx* ctx);                     // frees the gradient workspaces
 
 // ---- comm.cpp -----------------------------------------------------------------------------------------------------------
 void comm_release(mcalf_ctx* ctx);

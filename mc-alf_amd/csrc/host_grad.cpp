@@ -1,0 +1,146 @@
+// Host side of the analytic gradient of logL (grad_kernels.hip): mcalf_loglike_grad_batch[_device] and
+// mcalf_voigt_hjerting_grad.  logL itself comes from the likelihood's own launch (host_abi.cpp: launch), so the two
+// entries agree on it bit for bit; the gradient kernels then run over row blocks whose per-row workspaces stay within
+// kGradChunkBytes.
+#include <cmath>
+
+#include "grad_args.h"
+#include "host_ctx.h"
+
+namespace {
+
+int grad_ntiles(const mcalf_ctx* ctx) { return (int)((ctx->npix + kGradBlock - 1) / kGradBlock); }
+int grad_nslots(const mcalf_ctx* ctx) { return std::max(1, ctx->ncompmax * ctx->nlines + ctx->nfill); }
+int grad_ncap(const mcalf_ctx* ctx) {
+    return ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? ctx->jax_half : (ctx->wide ? ctx->wide_n_cap : ctx->n_cap);
+}
+int grad_tapcap(const mcalf_ctx* ctx) { return 2 * grad_ncap(ctx) + 1; }
+
+// Rows per pass: EVERY per-row workspace of a pass (F, q, taps and their R derivative, records, partials) within
+// kGradChunkBytes -- the taps of a wide-LSF context are thousands of doubles per row.
+int64_t grad_chunk_rows(const mcalf_ctx* ctx) {
+    const int64_t per_row = (2 * (int64_t)ctx->npix + 2 * (int64_t)grad_tapcap(ctx) + kGradRow +
+                             (int64_t)grad_nslots(ctx) * kGradRec + (int64_t)grad_ntiles(ctx) * ctx->ndim) * (int64_t)sizeof(double);
+    return std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row);
+}
+
+// Everything a pass of `rows` rows needs, grown once (a later call of as many rows or fewer allocates nothing).
+int grad_prepare(mcalf_ctx* ctx, int64_t batch) {
+    const size_t rows = (size_t)std::min<int64_t>(batch, grad_chunk_rows(ctx));
+    int rc;
+    if ((rc = grow(ctx, &ctx->g_rows, &ctx->cap_g_rows, rows * kGradRow))) return rc;
+    if ((rc = grow(ctx, &ctx->g_recs, &ctx->cap_g_recs, rows * grad_nslots(ctx) * kGradRec))) return rc;
+    if ((rc = grow(ctx, &ctx->g_taps, &ctx->cap_g_taps, rows * grad_tapcap(ctx)))) return rc;
+    if ((rc = grow(ctx, &ctx->g_dtaps, &ctx->cap_g_dtaps, rows * grad_tapcap(ctx)))) return rc;
+    if ((rc = grow(ctx, &ctx->g_F, &ctx->cap_g_F, rows * ctx->npix))) return rc;
+    if ((rc = grow(ctx, &ctx->g_q, &ctx->cap_g_q, rows * ctx->npix))) return rc;
+    return grow(ctx, &ctx->g_part, &ctx->cap_g_part, rows * grad_ntiles(ctx) * ctx->ndim);
+}
+
+// logL of the batch (the likelihood's launch, which sizes its own workspaces -- per pass of rows on a wide-LSF context), then
+// the gradient kernels pass by pass; all on `stream`.
+int grad_launch(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG, hipStream_t stream) {
+    if (batch <= 0) return MCALF_OK;
+    int rc = grad_prepare(ctx, batch);
+    if (rc) return rc;
+    if ((rc = launch(ctx, kModeLogL, dP, batch, 0, 0, dlogL, nullptr, stream))) return rc;
+    GradArgs a = {};
+    a.nu = ctx->d_nu; a.obj = ctx->d_obj; a.ispec2 = ctx->d_ispec2; a.lgis = ctx->d_lgis; a.lines = ctx->d_lines;
+    a.rows = ctx->g_rows; a.recs = ctx->g_recs; a.taps = ctx->g_taps; a.dtaps = ctx->g_dtaps;
+    a.F = ctx->g_F; a.q = ctx->g_q; a.part = ctx->g_part;
+    a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = grad_ntiles(ctx); a.tapcap = grad_tapcap(ctx); a.nslots = grad_nslots(ctx);
+    a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax; a.nfill = ctx->nfill; a.startind = ctx->startind; a.endind = ctx->endind;
+    a.freespecres = ctx->freespecres; a.freecont = ctx->freecont; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0;
+    a.jax_half = ctx->jax_half; a.n_cap = grad_ncap(ctx);
+    a.specres_fixed = ctx->specres_fixed; a.contval_fixed = ctx->contval_fixed; a.velstep = ctx->velstep;
+    const int64_t chunk = grad_chunk_rows(ctx);
+    for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
+        const int64_t nrows = std::min(chunk, batch - row0);
+        a.P = dP + (size_t)row0 * ctx->ndim;
+        a.logL = dlogL + row0;
+        a.G = dG + (size_t)row0 * ctx->ndim;
+        a.nrows = (int)nrows;
+        void* args[] = {(void*)&a};
+        const dim3 px((unsigned)a.ntiles, (unsigned)nrows);
+        HIP_TRY(ctx, hipLaunchKernel(grad_setup_kernel_ptr(), dim3((unsigned)nrows), dim3(kGradBlock), args, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel(grad_forward_kernel_ptr(), px, dim3(kGradBlock), args, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel(grad_model_kernel_ptr(), px, dim3(kGradBlock), args, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel(grad_adjoint_kernel_ptr(), px, dim3(kGradBlock), args, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel(grad_deriv_kernel_ptr(), px, dim3(kGradBlock), args, 0, stream));
+        const int64_t cells = nrows * ctx->ndim;
+        HIP_TRY(ctx, hipLaunchKernel(grad_finalize_kernel_ptr(), dim3((unsigned)((cells + kGradBlock - 1) / kGradBlock)),
+                                     dim3(kGradBlock), args, 0, stream));
+    }
+    return MCALF_OK;
+}
+
+}  // namespace
+
+void grad_release(mcalf_ctx* ctx) {
+    double* bufs[] = {ctx->g_rows, ctx->g_recs, ctx->g_taps, ctx->g_dtaps, ctx->g_F, ctx->g_q, ctx->g_part, ctx->g_P, ctx->g_logL, ctx->g_G};
+    for (double* b : bufs)
+        if (b) (void)hipFree(b);
+}
+
+extern "C" int mcalf_loglike_grad_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG,
+                                               void* stream) {
+    if (!ctx || batch < 0 || (batch > 0 && (!dP || !dlogL || !dG))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
+    MCALF_SINGLE_ONLY(ctx, "mcalf_loglike_grad_batch_device");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    return grad_launch(ctx, dP, batch, dlogL, dG, (hipStream_t)stream);
+}
+
+extern "C" int mcalf_loglike_grad_batch(mcalf_ctx* ctx, const double* P, int64_t batch, double* logL, double* G) {
+    if (!ctx || batch < 0 || (batch > 0 && (!P || !G))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
+    if (batch == 0) return MCALF_OK;
+    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
+        struct GradShard { const double* P; double *logL, *G; int ndim; } c = {P, logL, G, ctx->ndim};
+        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
+            const GradShard* s = static_cast<const GradShard*>(arg);
+            return mcalf_loglike_grad_batch(static_cast<mcalf_ctx*>(sub), s->P + (size_t)lo * s->ndim, hi - lo,
+                                            s->logL ? s->logL + lo : nullptr, s->G + (size_t)lo * s->ndim);
+        }, &c);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)batch * ctx->ndim;
+    int rc;
+    if ((rc = grow(ctx, &ctx->g_P, &ctx->cap_g_P, cells))) return rc;
+    if ((rc = grow(ctx, &ctx->g_G, &ctx->cap_g_G, cells))) return rc;
+    if ((rc = grow(ctx, &ctx->g_logL, &ctx->cap_g_logL, (size_t)batch))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_P, P, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = grad_launch(ctx, ctx->g_P, batch, ctx->g_logL, ctx->g_G, ctx->stream))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(G, ctx->g_G, cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (logL) HIP_TRY(ctx, hipMemcpyAsync(logL, ctx->g_logL, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->last.path = MCALF_PATH_HOST_STAGED;              // H2D, launch, D2H on the context's stream (set after the launch's own)
+    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
+    ctx->last.pinned_out = is_pinned_host(G) ? 1 : 0;
+    return MCALF_OK;
+}
+
+extern "C" int mcalf_voigt_hjerting_grad(const double* x, const double* y, int64_t n, double* out, int32_t device) {
+    if (n < 0 || (n > 0 && (!x || !y || !out))) return set_err(nullptr, MCALF_ERR_INVALID, "bad arguments");
+    if (n == 0) return MCALF_OK;
+    int dev = 0;
+    int rc = pick_device(nullptr, device, &dev, nullptr);
+    if (rc) return rc;
+    HIP_TRY(nullptr, hipSetDevice(dev));
+    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    const size_t nb = (size_t)n * sizeof(double);
+    hipError_t e = hipMalloc((void**)&dx, nb);
+    if (e == hipSuccess) e = hipMalloc((void**)&dy, nb);
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, 3 * nb);
+    if (e == hipSuccess) e = hipMemcpy(dx, x, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dy, y, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        long cnt = (long)n;
+        void* kargs[] = {(void*)&dx, (void*)&dy, (void*)&cnt, (void*)&dout};
+        e = hipLaunchKernel(grad_hjert_kernel_ptr(), dim3((unsigned)((n + 255) / 256)), dim3(256), kargs, 0, nullptr);
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dout, 3 * nb, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = set_err(nullptr, MCALF_ERR_HIP, "hjerting_grad: %s", hipGetErrorString(e));
+    for (double* b : {dx, dy, dout})
+        if (b) (void)hipFree(b);
+    return rc;
+}

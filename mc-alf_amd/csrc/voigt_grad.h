@@ -1,0 +1,101 @@
+// Device Faddeeva function w(z) and its derivative w'(z) for the gradient path (grad_kernels.hip), float64, Im z >= 0.
+//
+// H(x, y) = Re w(x + i y) is the Voigt-Hjerting function the likelihood uses; the gradient needs its partials too:
+//     w'(z) = -2 z w(z) + 2 i / sqrt(pi),   H_x = Re w',   H_y = -Im w'.
+// The fused kernel's folded tables (voigt_device.h) are built for H alone; this file evaluates w directly:
+//
+//   |z| <   8 : Weideman's rational expansion (SIAM J. Numer. Anal. 31 (1994) 1497) with N = 40 terms,
+//               w = 2 p(Z) / (L - i z)^2 + (1/sqrt(pi)) / (L - i z),   Z = (L + i z) / (L - i z),   L = sqrt(N / sqrt 2);
+//               w' from the identity above (cancellation grows like 2|z|^2: <= 2e-13 relative at |z| = 8)
+//   |z| >=  8 : the Laplace asymptotic series  w = i/(sqrt(pi) z) sum_k (2k-1)!!/(2 z^2)^k, truncated by |z| (asym_terms:
+//               24 terms at |z| = 8 down to 4 from |z| = 1000, the bulk of a spectrum's pixels),
+//               its term-by-term derivative and that of z w (no cancellation)
+//
+// Accuracy (numpy restatement against 40-digit mpmath): |dw| <= 5e-15 |w|, |dw'| <= 2e-13 |w'|, e (below) <= 1e-15 relative
+// beyond |z| = 8, over |x| <= 3000, y in [1e-6, 10].  The 40 coefficients are Weideman's FFT of exp(-t^2)(L^2 + t^2) on
+// t = L tan(theta/2), highest degree first (his `cef` routine, evaluated in float64).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace mcalf {
+
+constexpr double kWeidL = 5.3182958969449885;
+constexpr int kWeidN = 40;
+constexpr double kGradInvSqrtPi = 0.56418958354775628695;
+constexpr double kAsymR2 = 64.0;      // |z|^2 from which the asymptotic series takes over
+
+// Terms of the asymptotic series that keep w, w' and (z w)' within 1e-15 relative over [|z|, next threshold) (checked against
+// 40-digit mpmath; the truncation error falls as |z| grows inside each bracket).  (z w)' starts at the k = 1 term, so its
+// relative truncation error is 2k|z|^2 times the last term's: that, not w, sets the counts.
+__device__ __forceinline__ int asym_terms(double r2) {
+    return r2 >= 1e6 ? 4 : r2 >= 1e4 ? 6 : r2 >= 900.0 ? 9 : r2 >= 225.0 ? 14 : 24;
+}
+
+__device__ __constant__ static const double kWeidCoef[kWeidN] = {
+    -1.73569809987918647e-15, 1.20167491075928095e-15, 1.15191702207494847e-14, -5.23171636632440398e-15,
+    -7.07108802215940845e-14, 1.37782240476640457e-14, 4.53414489094346555e-13, 1.20333095291956798e-13,
+    -2.90771851041427015e-12, -2.72777356258302445e-12, 1.77141856738671790e-11, 3.47274209389070152e-11,
+    -9.05513886095832302e-11, -3.56323504036026841e-10, 2.10859907312510581e-10, 3.01778042555156406e-09,
+    3.24974658294507890e-09, -1.83156168342968342e-08, -6.35177348301541098e-08, 1.41986423729534295e-08,
+    5.91213695302905726e-07, 1.48356611331720142e-06, -1.06601389841627292e-06, -1.80074471447234073e-05,
+    -5.59130926423487940e-05, -3.93936314548380510e-05, 4.39807015986967025e-04, 2.70540563307372899e-03,
+    1.00481862427835352e-02, 2.92029164712418812e-02, 7.18236177907432827e-02, 1.55042638024795038e-01,
+    2.99894379961500590e-01, 5.26652898827708604e-01, 8.47217457659381501e-01, 1.25638156757651331e+00,
+    1.72538308481797786e+00, 2.20151379487831189e+00, 2.61605415276185971e+00, 2.89962450938970484e+00,
+};
+
+// (wr, wi) = w(x + i y), (dr, di) = w'(x + i y), e = Re(w + z w') = H + x H_x + y H_y; y >= 0.
+// e is what d tau / d b needs; in the wings its terms cancel to O(1/|z|^2) of H (a damped line's Lorentzian wing does not
+// depend on b), so beyond |z| = 8 it is summed from its own series, (z w)' = i/sqrt(pi) sum_k -2k c_k z^(-2k-1).
+__device__ __forceinline__ void faddeeva_dw(double x, double y, double& wr, double& wi, double& dr, double& di, double& e) {
+    const double r2 = x * x + y * y;
+    if (r2 >= kAsymR2) {
+        // 1/(2 z^2) and the two sums s = sum c_k, sd = -sum (2k+1) c_k, c_0 = 1, c_{k+1} = c_k (2k+1)/(2 z^2)
+        // ONE division: 1/|z|^2, and |z^2|^2 = |z|^4
+        const double z2r = x * x - y * y, z2i = 2.0 * x * y;
+        const double rr2 = 1.0 / r2, rm2 = rr2 * rr2;
+        const double hr = 0.5 * z2r * rm2, hi = -0.5 * z2i * rm2;
+        double cr = 1.0, ci = 0.0, sr = 0.0, si = 0.0, tr = 0.0, ti = 0.0, er = 0.0, ei = 0.0;
+        const int nt = asym_terms(r2);
+        for (int k = 0; k < nt; ++k) {
+            sr += cr; si += ci;
+            tr -= (2 * k + 1) * cr; ti -= (2 * k + 1) * ci;
+            er -= (2 * k) * cr; ei -= (2 * k) * ci;
+            const double f = (double)(2 * k + 1);
+            const double nr = f * (cr * hr - ci * hi), ni = f * (cr * hi + ci * hr);
+            cr = nr; ci = ni;
+        }
+        // i/(sqrt(pi) z) = i conj(z) / (sqrt(pi) |z|^2) = (y + i x) / (sqrt(pi) r2)
+        const double ar = y * kGradInvSqrtPi * rr2, ai = x * kGradInvSqrtPi * rr2;
+        wr = ar * sr - ai * si;
+        wi = ar * si + ai * sr;
+        e = ar * er - ai * ei;
+        // i/(sqrt(pi) z^2) = i conj(z^2) / (sqrt(pi) |z|^4)
+        const double br = z2i * kGradInvSqrtPi * rm2, bi = z2r * kGradInvSqrtPi * rm2;
+        dr = br * tr - bi * ti;
+        di = br * ti + bi * tr;
+        return;
+    }
+    // L - i z = (L + y) - i x,  L + i z = (L - y) + i x
+    const double er = kWeidL + y, ei = -x;
+    const double em = er * er + ei * ei;
+    const double vr = er / em, vi = -ei / em;                     // 1/(L - i z)
+    const double ur = kWeidL - y, ui = x;
+    const double Zr = ur * vr - ui * vi, Zi = ur * vi + ui * vr;  // Z
+    double pr = kWeidCoef[0], pi = 0.0;
+#pragma unroll
+    for (int k = 1; k < kWeidN; ++k) {
+        const double nr = fma(pr, Zr, fma(-pi, Zi, kWeidCoef[k]));
+        pi = fma(pr, Zi, pi * Zr);
+        pr = nr;
+    }
+    const double v2r = vr * vr - vi * vi, v2i = 2.0 * vr * vi;
+    wr = 2.0 * (pr * v2r - pi * v2i) + kGradInvSqrtPi * vr;
+    wi = 2.0 * (pr * v2i + pi * v2r) + kGradInvSqrtPi * vi;
+    // w' = -2 z w + 2 i / sqrt(pi)
+    dr = -2.0 * (x * wr - y * wi);
+    di = -2.0 * (x * wi + y * wr) + 2.0 * kGradInvSqrtPi;
+    e = wr + (x * dr - y * di);
+}
+
+}  // namespace mcalf

@@ -407,6 +407,37 @@ class als_fitter:
             _lib.check(rc, self._ctx)
         return out
 
+    def loglike_grad_batch(self, P, out=None, grad_out=None):
+        """(logL, G) for every row: logL[i] = lnlhood_worker(P[i]) as `loglike_batch` gives it, and
+        G[i, k] = d logL[i] / d P[i, k], the analytic gradient under the context's `conv_mode` (HIP kernels).
+
+        The ncomp column and the (N, z, b) of every component at or beyond the row's active count are exactly 0;
+        rows whose logL is -inf (asymmetric veto) or NaN get an all-NaN row.  On the numpy path the LSF tap count
+        ceil(3.0348 sigma) is held at its value for the row: G is the derivative within that piece, while logL
+        itself jumps where the count changes; the R column is 0 when R <= velstep (no convolution).  `out` /
+        `grad_out` (float64, C-contiguous, [batch] / [batch, ndim]) are filled in place when given."""
+        P = self._rows(P, self.ndim)
+        n = P.shape[0]
+        if out is None:
+            out = np.empty(n)
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size != n:
+            raise ValueError("out must be a C-contiguous float64 array with one entry per row")
+        if grad_out is None:
+            grad_out = np.empty((n, self.ndim))
+        elif grad_out.dtype != np.float64 or not grad_out.flags.c_contiguous or grad_out.size != n * self.ndim:
+            raise ValueError("grad_out must be a C-contiguous float64 array of shape [batch, ndim]")
+        rc = self._lib.mcalf_loglike_grad_batch(self._ctx, self._ptr(P), n, self._ptr(out), self._ptr(grad_out))
+        if rc:
+            _lib.check(rc, self._ctx)
+        return out, grad_out.reshape(n, self.ndim)
+
+    def lnlhood_grad(self, p):
+        """(logL, gradient) of one parameter vector: `lnlhood_worker(p)` and its analytic gradient
+        (`loglike_grad_batch`).  Negated, it is what `scipy.optimize.minimize(..., jac=True)` takes."""
+        self._check_scalar(p)
+        ll, g = self.loglike_grad_batch(np.asarray(p, dtype=float).reshape(1, -1))
+        return float(ll[0]), g[0]
+
     def chi2_batch(self, P):
         P = self._rows(P, self.ndim)
         out = np.empty(P.shape[0])
@@ -569,7 +600,12 @@ class als_fitter:
         The closure is batch-capable: `p` of shape [..., ndim] gives float32 [...].  With JAX installed (and
         `use_jax` not False) it is wrapped in `jax.pure_callback`, so it can be traced, jitted and vmapped by
         jaxns exactly like the reference's closure; without JAX it is the plain host function.  `use_jax=True`
-        raises ImportError when JAX is absent, as the reference does (:523-524)."""
+        raises ImportError when JAX is absent, as the reference does (:523-524).
+
+        Under JAX the closure is a `jax.custom_vjp`: its backward pass is a `pure_callback` into the twin's analytic
+        gradient (`loglike_grad_batch`, float32 in and out), so `jax.grad` works on it as on the reference's plain-JAX
+        closure.  The host half of that pass is `.host_grad(p) -> (logL, G)` (float32, G of shape p.shape), on both
+        the JAX-wrapped and the plain closure."""
         twin = self if self.conv_mode == "jax" else self._jax_twin()
         ndim = self.ndim
 
@@ -581,6 +617,15 @@ class als_fitter:
             ll = twin.loglike_batch(rows).astype(np.float32)
             return ll.reshape(p32.shape[:-1]) if p32.ndim > 1 else ll.reshape(())[()]
 
+        def host_grad(p):
+            p32 = np.asarray(p, dtype=np.float32)
+            if p32.shape[-1:] != (ndim,):
+                raise ValueError(f"parameter vectors must have {ndim} entries")
+            rows = np.ascontiguousarray(p32.reshape(-1, ndim), dtype=np.float64)
+            ll, g = twin.loglike_grad_batch(rows)
+            ll = ll.astype(np.float32)
+            return (ll.reshape(p32.shape[:-1]) if p32.ndim > 1 else ll.reshape(())[()]), g.astype(np.float32).reshape(p32.shape)
+
         try:
             if use_jax is False:
                 raise ImportError
@@ -590,15 +635,33 @@ class als_fitter:
             if use_jax:
                 raise ImportError("JAX is not available.")
             host_loglike.fitter = twin
+            host_loglike.host_grad = host_grad
             return host_loglike
 
-        def log_likelihood(p):                                           # pragma: no cover - needs JAX
-            p = jnp.asarray(p, dtype=jnp.float32)
+        def value(p):                                                    # pragma: no cover - needs JAX
             shape = jax.ShapeDtypeStruct(p.shape[:-1], jnp.float32)
             return jax.pure_callback(lambda q: np.asarray(host_loglike(q), dtype=np.float32).reshape(q.shape[:-1]),
                                      shape, p, vmap_method="expand_dims")
+
+        @jax.custom_vjp
+        def log_likelihood(p):                                           # pragma: no cover - needs JAX
+            return value(jnp.asarray(p, dtype=jnp.float32))
+
+        def fwd(p):                                                      # pragma: no cover - needs JAX
+            p = jnp.asarray(p)
+            return value(p.astype(jnp.float32)), p
+
+        def bwd(p, ct):                                                  # pragma: no cover - needs JAX
+            # the callback is float32 in and out; the cotangent goes back in the primal's dtype (float64 under x64)
+            p32 = p.astype(jnp.float32)
+            g = jax.pure_callback(lambda q: np.asarray(host_grad(q)[1], dtype=np.float32).reshape(q.shape),
+                                  jax.ShapeDtypeStruct(p32.shape, jnp.float32), p32, vmap_method="expand_dims")
+            return ((jnp.asarray(ct, dtype=jnp.float32)[..., None] * g).astype(p.dtype),)
+
+        log_likelihood.defvjp(fwd, bwd)
         log_likelihood.fitter = twin
         log_likelihood.host = host_loglike
+        log_likelihood.host_grad = host_grad
         return log_likelihood
 
     def _jax_twin(self):
