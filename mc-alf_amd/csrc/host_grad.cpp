@@ -17,11 +17,14 @@ int grad_ncap(const mcalf_ctx* ctx) {
 int grad_tapcap(const mcalf_ctx* ctx) { return 2 * grad_ncap(ctx) + 1; }
 
 // Rows per pass: EVERY per-row workspace of a pass (F, q, taps and their R derivative, records, partials) within
-// kGradChunkBytes -- the taps of a wide-LSF context are thousands of doubles per row.
+// kGradChunkBytes -- the taps of a wide-LSF context are thousands of doubles per row -- and at most kGradMaxRows rows:
+// the pixel kernels carry the row on grid.y (a short spectrum's rows are ~2 KB each, so the byte bound alone would
+// allow ~200 000 of them), the same cap as the likelihood's wide path (host_abi.cpp: wide_rows_per_pass).
+constexpr int64_t kGradMaxRows = 65535;
 int64_t grad_chunk_rows(const mcalf_ctx* ctx) {
     const int64_t per_row = (2 * (int64_t)ctx->npix + 2 * (int64_t)grad_tapcap(ctx) + kGradRow +
                              (int64_t)grad_nslots(ctx) * kGradRec + (int64_t)grad_ntiles(ctx) * ctx->ndim) * (int64_t)sizeof(double);
-    return std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row);
+    return std::min<int64_t>(kGradMaxRows, std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row));
 }
 
 // Everything a pass of `rows` rows needs, grown once (a later call of as many rows or fewer allocates nothing).

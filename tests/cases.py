@@ -20,6 +20,73 @@ def problem_from_kwargs(kw):
         fitrange=kw.get("fitrange"), velstep=kw.get("velstep"))
 
 
+BAD_KINDS = ("flux_nan", "err_nan", "err_zero")      # each drops the pixel's term from np.nansum (hires_fitter.py:292-294)
+
+
+def with_bad_pixels(kw, idx, kind):
+    """The kwargs `kw` of a finite problem with the FITTED pixels `idx` (indices after the fitrange selection, the
+    library's own pixel numbering) made bad: `kind` is one of 'flux_nan', 'err_nan', 'err_zero' (the term is NaN and
+    nansum drops it), 'err_neg' (squared away: a control, nothing is dropped), 'err_inf' / 'flux_inf' (term +inf,
+    logL = -inf), or one such name per index."""
+    wl, flux, err = (np.array(a, dtype=float) for a in kw["spectrum"])
+    ok = np.zeros(wl.size, dtype=bool)
+    for lo, hi in kw["fitrange"]:
+        ok |= (wl > lo) & (wl < hi)
+    at = np.flatnonzero(ok)[np.asarray(idx, dtype=int)]
+    kinds = [kind] * at.size if isinstance(kind, str) else list(kind)
+    assert len(kinds) == at.size
+    for i, k in zip(at, kinds):
+        if k == "flux_nan":
+            flux[i] = np.nan
+        elif k == "err_nan":
+            err[i] = np.nan
+        elif k == "err_zero":
+            err[i] = 0.0
+        elif k == "err_neg":
+            err[i] = -err[i]
+        elif k == "err_inf":
+            err[i] = np.inf
+        elif k == "flux_inf":
+            flux[i] = np.inf
+        else:
+            raise ValueError(k)
+    return dict(kw, spectrum=(wl, flux, err))
+
+
+HI_1215 = (1215.67, 0.4164, 6.265e8)
+ASYM_BRACKETS = (64.0, 225.0, 900.0, 1e4, 1e6, np.inf)      # |z|^2 edges of voigt_grad.h: asym_terms (24, 14, 9, 6, 4 terms)
+
+
+def wing_only_problem(npix=3000, seed=5):
+    """(kwargs, rows) of a damped HI 1215 component at z = 0 seen ONLY in its red wing: a logarithmic grid from +300 to
+    +12000 km/s of the line centre, no filler.  Every pixel of every row has |u| >= 8.5, so the gradient's Voigt
+    evaluations all come from the asymptotic series and the b column is e = H + u H_u + a H_a alone, without a line core
+    to dominate its scale S_b; the (logN, b) of the rows spread the pixels over all five truncation brackets of that
+    series (`bracket_counts`).  The data are the model of (logN, b) = (20.5, 25) plus noise: no row fits them, so q is not
+    noise alone and S_b is 2 .. 8 on every row."""
+    step = (12000.0 - 300.0) / (npix - 1)
+    wl = HI_1215[0] * np.exp((300.0 + step * np.arange(npix)) / 2.9979245e5)
+    err = np.full(npix, 0.02)
+    kw = dict(fitrange=[[wl[0] - 1e-3, wl[-1] + 1e-3]], fitlines=["HI 1215"], linepars=[HI_1215], ncomp=[1, 1], nfill=0,
+              specres=[8.0], Nrange=[12.0, 21.0], brange=[5.0, 100.0], zrange=[-1e-4, 1e-4], velstep=float(step),
+              spectrum=(wl, np.ones(npix), err))
+    P = np.array([[1.0, 20.3, 0.0, 30.0], [1.0, 19.5, 2e-5, 12.0], [1.0, 20.8, -3e-5, 35.0], [1.0, 20.0, 1e-5, 6.0]])
+    flux = oracle_synth(kw, np.array([1.0, 20.5, 0.0, 25.0])) + np.random.default_rng(seed).normal(0, 0.02, npix)
+    return dict(kw, spectrum=(wl, flux, err)), P
+
+
+def bracket_counts(prob, p):
+    """(min |u|, pixels per `ASYM_BRACKETS` bracket of |z|^2) of the single component of row `p`, from the reference's own
+    u = (nu (1 + z) - nu0) / dnu and a (hires_fitter.py:357-362)."""
+    s = prob.startind
+    logN, z, b = p[s + 1:s + 4]
+    wrest, f, gam = prob.lines[0]
+    dnu = b * 1e5 / (wrest / 1e8)
+    u = (oracle.CCGS / (prob.wl / 1e8) * (z + 1.0) - oracle.CCGS / (wrest / 1e8)) / dnu
+    a = gam / (4 * np.pi * dnu)
+    return np.abs(u).min(), np.histogram(u * u + a * a, bins=ASYM_BRACKETS)[0]
+
+
 def oracle_synth(kw, p):
     return oracle.reconstruct_spec(problem_from_kwargs(kw), p)
 

@@ -1,11 +1,15 @@
 """CPU: the test-side gradient reference (tests/grad_reference.py) against central differences of the oracle's logL, on
-both convolution paths, with a fixed and a free resolution / continuum, R <= velstep, and fractional / negative ncomp.
-The GPU gradient (tests/test_gpu_grad.py) is checked against this reference, so this is what anchors it."""
+both convolution paths, with a fixed and a free resolution / continuum, R <= velstep, and fractional / negative ncomp;
+on a spectrum with bad pixels (NaN flux, NaN error, zero error: the terms nansum drops) and on a damped line seen only in
+its wing (every Voigt evaluation from the asymptotic series).  Worst |G - central difference| / S there: 5.4e-8 (bad
+pixels, numpy path), 1.2e-7 (bad pixels, JAX path), 8.6e-8 (wing only) against the bar of 1e-5.
+The GPU gradient (tests/test_gpu_grad.py, test_gpu_bad_pixels.py, test_gpu_grad_edges.py) is checked against this
+reference, so this is what anchors it."""
 import numpy as np
 import pytest
 
 import grad_reference as gr
-from cases import problem_from_kwargs
+from cases import ASYM_BRACKETS, bracket_counts, problem_from_kwargs, wing_only_problem, with_bad_pixels
 from mcalf_amd import workloads
 
 CIV = [(1548.204, 0.1899, 2.643e8), (1550.781, 0.09475, 2.628e8)]
@@ -52,20 +56,65 @@ CASES = {
 }
 
 
+def bad_pixel_problem(**kwargs):
+    """The 600-pixel CIV problem with 49 bad pixels of the three kinds: the two ends, both sides of pixel 256, a run of 20
+    and a random 25."""
+    kw = _kw(**kwargs)
+    rng = np.random.default_rng(17)
+    idx = np.unique(np.concatenate([[0, 255, 256, 599], np.arange(300, 320), rng.choice(np.arange(1, 599), 60, replace=False)]))[:49]
+    idx[-1] = 599
+    kinds = [("flux_nan", "err_nan", "err_zero")[k % 3] for k in range(idx.size)]
+    return with_bad_pixels(kw, idx, kinds)
+
+
+CASES["numpy_bad_pixels"] = (bad_pixel_problem(specres=(6.0, 9.0), contval=(0.9, 1.1)), False)
+CASES["jax_bad_pixels"] = (bad_pixel_problem(specres=(6.0, 9.0), contval=(0.9, 1.1)), True)
+
+
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_reference_matches_central_differences(name):
     kw, jax = CASES[name]
     prob = problem_from_kwargs(kw)
     P = _away_from_tap_jumps(prob, _rows(kw, 3, seed=len(name)))
     cols = [k for k in range(prob.ndim) if k != prob.startind]
+    if "bad_pixels" in name:
+        assert (~np.isfinite(prob.flux) | ~(np.abs(prob.err) > 0)).sum() == 49
     for p in P:
-        logl, G, S = gr.grad_row(prob, p, jax=jax)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            logl, G, S = gr.grad_row(prob, p, jax=jax)
+            cd = gr.central_differences(prob, p, cols, jax=jax)
         assert np.isfinite(logl)
-        cd = gr.central_differences(prob, p, cols, jax=jax)
         for k in cols:
             assert abs(G[k] - cd[k]) <= 1e-5 * S[k], (name, k, G[k], cd[k], S[k])
         if name == "numpy_R_le_velstep":
             assert prob.velstep >= max(prob.specres)
+
+
+def test_reference_on_a_wing_only_damped_line():
+    """The wing-only problem of tests/cases.py: every pixel beyond |u| = 8.5, all five truncation brackets of the
+    kernels' asymptotic series populated, and S_b free of a line core.  Steps 1e-5 (1e-7 (1 + z) for z): the default ones
+    are noise-limited at |logL| ~ 2e5."""
+    kw, P = wing_only_problem()
+    prob = problem_from_kwargs(kw)
+    total = np.zeros(len(ASYM_BRACKETS) - 1, dtype=int)
+    cols = [k for k in range(prob.ndim) if k != prob.startind]
+    for p in P:
+        umin, counts = bracket_counts(prob, p)
+        assert umin >= 8.5 and counts.sum() == prob.wl.size
+        total += counts
+        logl, G, S = gr.grad_row(prob, p)
+        assert np.isfinite(logl) and S[prob.startind + 3] > 1.0          # (the 1e-9 floor of the GPU bar is negligible)
+        cd = gr.central_differences(prob, p, cols, rel=1e-5, rel_z=1e-7)
+        for k in cols:
+            assert abs(G[k] - cd[k]) <= 1e-5 * S[k], (p, k, G[k], cd[k], S[k])
+    assert np.all(total >= 20), total
+
+
+def test_err_inf_is_minus_inf_with_a_nan_gradient():
+    prob = problem_from_kwargs(with_bad_pixels(_kw(), [7], "err_inf"))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        logl, G, _ = gr.grad_row(prob, _rows(_kw(), 1, seed=1)[0])
+    assert logl == -np.inf and np.all(np.isnan(G))
 
 
 def test_reference_zero_and_nan_columns():
