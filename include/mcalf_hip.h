@@ -63,7 +63,7 @@
 extern "C" {
 #endif
 
-#define MCALF_ABI_VERSION 8   /* 2: mcalf_last_launch, gatherv / overlap / join, version string carries the source hash
+#define MCALF_ABI_VERSION 9   /* 2: mcalf_last_launch, gatherv / overlap / join, version string carries the source hash
                                  3: MCALF_PATH_HOST_STREAM, mcalf_launch_info_t grows by stream_setup_wgs / stream_polled
                                  4: mcalf_broker_serve
                                  5: mcalf_set_resident, mcalf_broker_serve_resident
@@ -72,7 +72,9 @@ extern "C" {
                                     was built for, and checked after every launch)
                                  7: mcalf_create_multi, mcalf_last_launch_sub, mcalf_get_config; mcalf_info_t grows by ndevices /
                                     devices[16], mcalf_launch_info_t by devices_used
-                                 8: mcalf_loglike_grad_batch[_device], mcalf_voigt_hjerting_grad (the analytic gradient of logL) */
+                                 8: mcalf_loglike_grad_batch[_device], mcalf_voigt_hjerting_grad (the analytic gradient of logL)
+                                 9: mcalf_model_jvp_batch[_device], mcalf_model_vjp_batch[_device] (the model Jacobian's products
+                                    with a vector) */
 
 enum {
     MCALF_OK = 0,
@@ -313,6 +315,27 @@ int mcalf_loglike_grad_batch(mcalf_ctx* ctx, const double* P, int64_t batch, dou
  * batch it allocates and synchronises nothing. */
 int mcalf_loglike_grad_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG,
                                     void* stream);
+
+/* The model Jacobian's products with a vector, matrix-free.  J(P[i]) [k, c] = d m_k / d P[i, c] (npix x ndim) is the
+ * Jacobian of the full model m = mcalf_model_batch(targonly = 0) of row i under the context's conv_mode; it is never
+ * formed.  P, V, G are batch x ndim, Q and dM batch x npix, all row-major.
+ *   JVP:  dM[i, :] = J(P[i]) V[i, :]     the directional derivative of the model along a parameter tangent
+ *   VJP:  G[i, :]  = J(P[i])^T Q[i, :]   the caller's per-pixel cotangent pulled back to the parameters
+ * (the gradient of logL is the VJP of Q = (d - m) / err^2 on the pixels nansum keeps; a Fisher product J^T W J v is one
+ * JVP and one VJP).  ONE tangent or cotangent per row: the batch axis is the vector axis, so k vectors at one theta are
+ * k rows that repeat it.  Columns that are 0 by definition, as in the gradient: the ncomp slot and the (N, z, b) of every
+ * component at or beyond the row's active count -- those entries of V are ignored and those of G are exactly 0, as are
+ * the R / continuum entries when the context fixes them.  Q is used as given (non-finite entries propagate).  On the
+ * numpy path the LSF tap count is held at its value for the row; a row whose tap count exceeds what the context
+ * provisions (R beyond specres_max) gets an all-NaN row.  Host pointers, synchronous; a multi-device context cuts the
+ * batch into contiguous row blocks, one per device, written straight into the caller's arrays.  A row's result does not
+ * depend on its batch, its position or the device count (every reduction runs in a fixed order). */
+int mcalf_model_jvp_batch(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* dM);
+int mcalf_model_vjp_batch(mcalf_ctx* ctx, const double* P, const double* Q, int64_t batch, double* G);
+/* Same, device pointers, on the caller's stream (single-device contexts).  After one call of the same or a larger
+ * batch they allocate and synchronise nothing. */
+int mcalf_model_jvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* ddM, void* stream);
+int mcalf_model_vjp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dQ, int64_t batch, double* dG, void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -1,7 +1,7 @@
 """Build libmcalf_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 The library is nine translation units: two device files -- kernels.hip (the likelihood's kernels) and grad_kernels.hip
-(the analytic gradient's) -- and the host side of the C ABI -- host_abi.cpp, host_stream.cpp, host_config.cpp,
+(the analytic gradient's and the Jacobian products') -- and the host side of the C ABI -- host_abi.cpp, host_stream.cpp, host_config.cpp,
 host_multi.cpp, host_grad.cpp, broker.cpp, comm.cpp -- compiled as plain C++ against the HIP runtime API.  Objects are
 kept under csrc/obj/ so that an edit of a host file does not recompile the kernels (22 s), and an edit of the gradient's
 device files does not recompile the likelihood's."""

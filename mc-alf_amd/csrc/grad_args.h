@@ -1,4 +1,4 @@
-// What the gradient kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
+// What the gradient and Jacobian-product kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
 // workspace layout and the kernel entry points.  Plain C++ -- host_grad.cpp is compiled without the HIP language mode.
 // Not part of the kernel-source hash (mc-alf_amd/build.py): the fused kernel does not include it.
 #pragma once
@@ -27,6 +27,10 @@ struct GradArgs {
     int nrows, npix, ndim, ntiles, tapcap, nslots;
     int nlines, ncompmax, nfill, startind, endind, freespecres, freecont, jax, jax_half, n_cap;
     double specres_fixed, contval_fixed, velstep;
+    // the model Jacobian's products (appended: the gradient kernels' argument offsets stay as they were).  The JVP keeps
+    // T = -F dtau in `q`; the VJP points `q` at the caller's cotangent rows, which no kernel of its pass writes.
+    const double* V;          // JVP: tangent rows of this pass [nrows, ndim]
+    double* dM;               // JVP: directional derivative of the model [nrows, npix]
 };
 
 // grad_kernels.hip; every kernel takes (const GradArgs a), grid as stated
@@ -36,6 +40,10 @@ MCALF_INTERNAL const void* grad_model_kernel_ptr();      // grid = (ntiles, nrow
 MCALF_INTERNAL const void* grad_adjoint_kernel_ptr();    // grid = (ntiles, nrows): g = -F cont L^T q (in place of F)
 MCALF_INTERNAL const void* grad_deriv_kernel_ptr();      // grid = (ntiles, nrows): (N, z, b) partials
 MCALF_INTERNAL const void* grad_finalize_kernel_ptr();   // grid = ceil(nrows * ndim / kGradBlock): tiles summed in order
+MCALF_INTERNAL const void* vjp_model_kernel_ptr();       // grid = (ntiles, nrows): the model kernel with q = the caller's cotangent
+MCALF_INTERNAL const void* vjp_finalize_kernel_ptr();    // as finalize, without the logL veto rule
+MCALF_INTERNAL const void* jvp_forward_kernel_ptr();     // grid = (ntiles, nrows): F = exp(-tau), T = -F dtau along the row's tangent
+MCALF_INTERNAL const void* jvp_model_kernel_ptr();       // grid = (ntiles, nrows): dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F)
 MCALF_INTERNAL const void* grad_hjert_kernel_ptr();      // (const double* x, const double* y, long n, double* out): out[3i..] = H, H_x, H_y
 
 }  // namespace mcalf

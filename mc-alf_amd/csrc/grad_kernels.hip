@@ -17,6 +17,15 @@
 //   deriv    (tile, row): H, H_u, H_a of every active (component, line); per component the three weighted sums
 //   finalize (row, column): partials summed over tiles in order; -inf / NaN logL rows get NaN
 // The convolutions read the workspace in HBM, so any LSF width the likelihood accepts works.
+//
+// The same file holds the model Jacobian's two products with a vector (mcalf_model_jvp_batch / _vjp_batch), J = dm/dtheta:
+//   J v   (JVP)  setup, then
+//     jvp_forward (tile, row): ONE Voigt pass: tau and dtau = sum_c (ln10 tau_c v_N + K H_u (nu/dnu) v_z - (K/b) e v_b),
+//                              F = exp(-tau) -> F workspace, T = -F dtau -> q workspace
+//     jvp_model   (tile, row): dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F), one tap loop over F and T
+//   J^T q (VJP)  the gradient's own pass with the caller's cotangent in place of w (d - m): setup, forward, vjp_model (the
+//                continuum and R partials; the q workspace pointer IS the caller's Q), adjoint, deriv, vjp_finalize (no
+//                logL, so no veto rule: only rows whose tap count exceeds the cap are NaN)
 #include <hip/hip_runtime.h>
 
 #include "grad_args.h"
@@ -170,8 +179,9 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_forward_kernel(const Gr
     a.F[(size_t)r * a.npix + i] = exp(-tau);
 }
 
-__global__ __launch_bounds__(kGradBlock) void mcalf_grad_model_kernel(const GradArgs a) {
-    __shared__ double lds[kGradBlock];
+// kCot: q is the caller's cotangent (a.q points at it) instead of w (d - m).
+template <bool kCot>
+__device__ __forceinline__ void model_tile(const GradArgs& a, double* lds) {
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
     const RowInfo ri = row_info(a, r);
@@ -209,11 +219,16 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_model_kernel(const Grad
         } else {
             conv = F[i];                                                           // R <= velstep: no convolution (:445)
         }
-        const double is2 = a.ispec2[i];
-        const double res = a.obj[i] - ri.cont * conv;
-        const double term = is2 * res * res - a.lgis[i];
-        const double qv = isnan(term) ? 0.0 : is2 * res;                          // the pixels nansum keeps (:294)
-        a.q[(size_t)r * a.npix + i] = qv;
+        double qv;
+        if (kCot) {
+            qv = a.q[(size_t)r * a.npix + i];
+        } else {
+            const double is2 = a.ispec2[i];
+            const double res = a.obj[i] - ri.cont * conv;
+            const double term = is2 * res * res - a.lgis[i];
+            qv = isnan(term) ? 0.0 : is2 * res;                                    // the pixels nansum keeps (:294)
+            a.q[(size_t)r * a.npix + i] = qv;
+        }
         pc = qv * conv;
         pR = qv * ri.cont * dconv;
     }
@@ -225,6 +240,16 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_model_kernel(const Grad
         if (a.freecont) out[a.freespecres ? 1 : 0] = pc;
         out[a.startind] = 0.0;                                                     // the ncomp slot
     }
+}
+
+__global__ __launch_bounds__(kGradBlock) void mcalf_grad_model_kernel(const GradArgs a) {
+    __shared__ double lds[kGradBlock];
+    model_tile<false>(a, lds);
+}
+
+__global__ __launch_bounds__(kGradBlock) void mcalf_vjp_model_kernel(const GradArgs a) {
+    __shared__ double lds[kGradBlock];
+    model_tile<true>(a, lds);
 }
 
 __global__ __launch_bounds__(kGradBlock) void mcalf_grad_adjoint_kernel(const GradArgs a) {
@@ -295,20 +320,113 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_deriv_kernel(const Grad
         }
 }
 
-__global__ __launch_bounds__(kGradBlock) void mcalf_grad_finalize_kernel(const GradArgs a) {
+// kVeto: rows whose logL is -inf (veto) or NaN get NaN too (the VJP has no logL).
+template <bool kVeto>
+__device__ __forceinline__ void finalize_cell(const GradArgs& a) {
     const long e = (long)blockIdx.x * kGradBlock + threadIdx.x;
     if (e >= (long)a.nrows * a.ndim) return;
     const int r = (int)(e / a.ndim), k = (int)(e - (long)r * a.ndim);
-    const double lg = a.logL[r];
+    const double lg = kVeto ? a.logL[r] : 0.0;
     double s;
     if (a.rows[(size_t)r * kGradRow + 4] != 0.0 || !(lg > -INFINITY)) {
-        s = NAN;                                                                    // veto (-inf) or NaN row
+        s = NAN;                                                                    // too many taps, veto (-inf) or NaN row
     } else {
         s = 0.0;
         const double* p = a.part + (size_t)r * a.ntiles * a.ndim + k;
         for (int t = 0; t < a.ntiles; ++t) s += p[(size_t)t * a.ndim];
     }
     a.G[(size_t)r * a.ndim + k] = s;
+}
+
+__global__ __launch_bounds__(kGradBlock) void mcalf_grad_finalize_kernel(const GradArgs a) { finalize_cell<true>(a); }
+
+__global__ __launch_bounds__(kGradBlock) void mcalf_vjp_finalize_kernel(const GradArgs a) { finalize_cell<false>(a); }
+
+// JVP, the one Voigt pass: per pixel tau and its directional derivative along the row's tangent.  The per-slot arithmetic
+// is mcalf_grad_deriv_kernel's, contracted with v instead of reduced over pixels.  Records and tangent entries are
+// row-uniform (scalar loads); the ncomp slot of v and the (N, z, b) of inactive components are never read.
+__global__ __launch_bounds__(kGradBlock) void mcalf_jvp_forward_kernel(const GradArgs a) {
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * kGradBlock + threadIdx.x;
+    if (i >= a.npix) return;
+    const RowInfo ri = row_info(a, r);
+    const double* v = a.V + (size_t)r * a.ndim;
+    const double nu = a.nu[i];
+    double tau = 0.0, dtau = 0.0;
+    const int ncomp = ri.nc + a.nfill;                 // active targets, then the fillers
+    for (int c = 0; c < ncomp; ++c) {
+        const bool fill = c >= ri.nc;
+        const int slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
+        const int nl = fill ? 1 : a.nlines;
+        const int col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
+        double sN = 0.0, sz = 0.0, sb = 0.0;
+        for (int l = 0; l < nl; ++l) {
+            const double* rec = rec_of(a, r, slot0 + l);
+            const double u = nu * rec[0] - rec[1], y = rec[2], K = rec[3];
+            double wr, wi, dr, di, e;
+            faddeeva_dw(u, y, wr, wi, dr, di, e);
+            sN += K * wr;                                   // tau
+            sz += K * dr * (nu * rec[4]);                   // K H_u du/dz
+            sb -= K * rec[5] * e;                           // (K/b)(H + u H_u + a H_a)
+        }
+        tau += sN;
+        dtau += kLn10 * sN * v[col] + sz * v[col + 1] + sb * v[col + 2];
+    }
+    const double F = exp(-tau);
+    a.F[(size_t)r * a.npix + i] = F;
+    a.q[(size_t)r * a.npix + i] = -F * dtau;
+}
+
+// JVP, the convolutions: dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F), the three modes of model_tile.
+__global__ __launch_bounds__(kGradBlock) void mcalf_jvp_model_kernel(const GradArgs a) {
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * kGradBlock + threadIdx.x;
+    if (i >= a.npix) return;
+    const RowInfo ri = row_info(a, r);
+    double* out = a.dM + (size_t)r * a.npix;
+    if (ri.bad) {                                                                  // more taps than the context provisions
+        out[i] = NAN;
+        return;
+    }
+    const double* F = a.F + (size_t)r * a.npix;
+    const double* T = a.q + (size_t)r * a.npix;
+    const double* taps = a.taps + (size_t)r * a.tapcap;
+    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
+    const double* v = a.V + (size_t)r * a.ndim;
+    const double vR = a.freespecres ? v[0] : 0.0;
+    const double vc = a.freecont ? v[a.freespecres ? 1 : 0] : 0.0;
+    double cF, cT, dF = 0.0;
+    if (a.jax) {
+        const int h = ri.n;
+        if (i < h || i >= a.npix - h) {
+            cF = F[i]; cT = T[i];                                                  // edge reset
+        } else {
+            double c = 0.0, d = 0.0, ct = 0.0;
+            for (int k = 0; k <= 2 * h; ++k) {
+                const double f = F[i + k - h];
+                c += taps[k] * f;
+                d += dtaps[k] * f;
+                ct += taps[k] * T[i + k - h];
+            }
+            cF = c; dF = d; cT = ct;
+        }
+    } else if (ri.n > 0) {
+        const int n = ri.n;
+        int j = (int)(((long)i - n) % a.npix);
+        if (j < 0) j += a.npix;
+        double c = 0.0, d = 0.0, ct = 0.0;
+        for (int k = 0; k <= 2 * n; ++k) {                                         // periodic boundary
+            const double f = F[j];
+            c += taps[k] * f;
+            d += dtaps[k] * f;
+            ct += taps[k] * T[j];
+            if (++j == a.npix) j = 0;
+        }
+        cF = c / ri.bot; dF = d / ri.bot; cT = ct / ri.bot;
+    } else {
+        cF = F[i]; cT = T[i];                                                      // R <= velstep: no convolution
+    }
+    out[i] = ri.cont * cT + vc * cF + vR * ri.cont * dF;
 }
 
 __global__ void mcalf_grad_hjert_kernel(const double* x, const double* y, long n, double* out) {
@@ -328,5 +446,9 @@ const void* grad_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcal
 const void* grad_adjoint_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_adjoint_kernel); }
 const void* grad_deriv_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_deriv_kernel); }
 const void* grad_finalize_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_finalize_kernel); }
+const void* vjp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_vjp_model_kernel); }
+const void* vjp_finalize_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_vjp_finalize_kernel); }
+const void* jvp_forward_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_jvp_forward_kernel); }
+const void* jvp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_jvp_model_kernel); }
 const void* grad_hjert_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_hjert_kernel); }
 }  // namespace mcalf

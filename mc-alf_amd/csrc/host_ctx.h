@@ -262,12 +262,12 @@ struct mcalf_ctx {
     SampleHdr* d_whdr = nullptr;
     size_t cap_wide = 0, cap_wtaps = 0, cap_wpartial = 0, cap_wrows = 0, cap_whdr = 0;
     mcalf_launch_info_t last = {};      // what the last call did (mcalf_last_launch)
-    // Gradient entries (host_grad.cpp): per-row workspaces of one pass, F / q of its rows, per-tile partials, and the
-    // parameter / logL / gradient rows of the host-pointer entry (all grown on demand)
+    // Gradient and Jacobian-product entries (host_grad.cpp): per-row workspaces of one pass, F / q of its rows, per-tile
+    // partials, and the parameter / logL / gradient (or tangent) / pixel rows of the host-pointer entries (all grown on demand)
     double *g_rows = nullptr, *g_recs = nullptr, *g_taps = nullptr, *g_dtaps = nullptr, *g_F = nullptr, *g_q = nullptr, *g_part = nullptr;
-    double *g_P = nullptr, *g_logL = nullptr, *g_G = nullptr;
+    double *g_P = nullptr, *g_logL = nullptr, *g_G = nullptr, *g_X = nullptr;
     size_t cap_g_rows = 0, cap_g_recs = 0, cap_g_taps = 0, cap_g_dtaps = 0, cap_g_F = 0, cap_g_q = 0, cap_g_part = 0;
-    size_t cap_g_P = 0, cap_g_logL = 0, cap_g_G = 0;
+    size_t cap_g_P = 0, cap_g_logL = 0, cap_g_G = 0, cap_g_X = 0;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).

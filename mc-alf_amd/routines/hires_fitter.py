@@ -438,6 +438,59 @@ class als_fitter:
         ll, g = self.loglike_grad_batch(np.asarray(p, dtype=float).reshape(1, -1))
         return float(ll[0]), g[0]
 
+    def _deriv_call(self, fn, P, X, xw, out, yw, what):
+        P = self._rows(P, self.ndim)
+        n = P.shape[0]
+        X = np.ascontiguousarray(X, dtype=float)
+        if X.ndim == 1:
+            X = X.reshape(1, -1)
+        if X.shape != (n, xw):
+            raise ValueError(f"{what} must have shape [{n}, {xw}], got {list(X.shape)}")
+        if out is None:
+            out = np.empty((n, yw))
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size != n * yw:
+            raise ValueError(f"out must be a C-contiguous float64 array of shape [batch, {yw}]")
+        rc = fn(self._ctx, self._ptr(P), self._ptr(X), n, self._ptr(out))
+        if rc:
+            _lib.check(rc, self._ctx)
+        return out.reshape(n, yw)
+
+    def model_jvp_batch(self, P, V, out=None):
+        """dM[i, :] = J(P[i]) V[i, :], the directional derivative of the model `model_batch(P)[i]` along the parameter
+        tangent V[i] ([batch, ndim] -> [batch, npix]; HIP kernels, the Jacobian J = d model / d theta is never formed).
+
+        One tangent per row: k tangents at one theta are k rows that repeat it.  The ncomp entry of V and the (N, z, b)
+        of components at or beyond the row's active count are ignored, as are the R / continuum entries the context
+        fixes; on the numpy path the LSF tap count is held at its value for the row (as in `loglike_grad_batch`).  A
+        row whose R needs more taps than the context provisions is all NaN.  `out` is filled in place when given."""
+        return self._deriv_call(self._lib.mcalf_model_jvp_batch, P, V, self.ndim, out, self.obj_wl.size, "V")
+
+    def model_vjp_batch(self, P, Q, out=None):
+        """G[i, :] = J(P[i])^T Q[i, :]: the per-pixel cotangent Q[i] ([batch, npix]) pulled back to the parameters
+        ([batch, ndim]) -- the gradient of any scalar of the model whose pixel derivative is Q.  `loglike_grad_batch` is
+        the special case Q = (flux - model) / err^2 on the pixels nansum keeps.
+
+        Q is used as given (non-finite entries propagate).  The ncomp column and the (N, z, b) of inactive components
+        are exactly 0; a row whose R needs more taps than the context provisions is all NaN."""
+        return self._deriv_call(self._lib.mcalf_model_vjp_batch, P, Q, self.obj_wl.size, out, self.ndim, "Q")
+
+    def fisher_matvec_batch(self, P, V):
+        """(J^T W J) V[i] per row, the Fisher matrix of the Gaussian likelihood at P[i] applied to V[i], matrix-free:
+        one `model_jvp_batch` and one `model_vjp_batch`.  W = 1 / err^2 on the pixels whose logL term np.nansum keeps
+        (finite flux, finite non-zero error) and 0 elsewhere."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w = 1.0 / np.asarray(self.obj_noise, dtype=float) ** 2
+            w = np.where(np.isnan(w * np.asarray(self.obj, dtype=float) ** 2 - np.log(w)), 0.0, w)
+        return self.model_vjp_batch(P, w * self.model_jvp_batch(P, V))
+
+    def model_jacobian(self, p):
+        """J[npix, ndim] = d model / d theta at one parameter vector: one `model_jvp_batch` call of ndim rows that
+        repeat `p`, with the identity's rows as tangents.  It costs ndim Voigt passes over the spectrum; for products
+        with a vector use `model_jvp_batch` / `model_vjp_batch`, which never form J."""
+        self._check_scalar(p)
+        P = np.tile(np.asarray(p, dtype=float).reshape(1, -1), (self.ndim, 1))
+        return np.ascontiguousarray(self.model_jvp_batch(P, np.eye(self.ndim)).T)
+
     def chi2_batch(self, P):
         P = self._rows(P, self.ndim)
         out = np.empty(P.shape[0])
