@@ -64,6 +64,9 @@ def _jvp_compare(dM, Js, V, what):
         want, S = mdr.jvp(J, np.where(np.isnan(V[r]), 0.0, V[r]))
         d = np.abs(dM[r] - want)
         assert np.isfinite(dM[r]).all(), (what, r)
+        if S.max() == 0.0:                             # J v is 0 by definition (nothing active, or F = 0 on every pixel): exactly 0
+            assert np.all(dM[r] == 0.0), (what, r)     # (0 / 0 below would hide the row from np.max)
+            continue
         worst = max(worst, float(np.max(d / (1e-7 * S + FLOOR_REL * S.max()))))
         lo = S < 1e-6 * S.max()
         if lo.any():
