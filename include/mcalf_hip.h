@@ -20,6 +20,7 @@
  *   mcalf_loglike_cube_batch <- lnlhood_pc(_scale_cube_pc(cube))      hires_fitter.py:202-209,250-262
  *   mcalf_loglike_grad_batch <- jax.grad of the get_jax_likelihood closure  hires_fitter.py:521-695
  *                             (no counterpart on the numpy path: finite differences of lnlhood_worker)
+ *   mcalf_loglike_hvp_batch  <- jax.jvp(jax.grad(...)) / jax.hessian of the same closure   hires_fitter.py:521-695
  *   mcalf_voigt_hjerting[_nodes] <- scipy.special.wofz(u + i a).real  hires_fitter.py:365
  *                             / voigt_jax.hjert                       voigt_jax.py:121-127
  *   mcalf_set_cu_mask, mcalf_stream_partition
@@ -74,7 +75,9 @@ extern "C" {
                                     devices[16], mcalf_launch_info_t by devices_used
                                  8: mcalf_loglike_grad_batch[_device], mcalf_voigt_hjerting_grad (the analytic gradient of logL)
                                  9: mcalf_model_jvp_batch[_device], mcalf_model_vjp_batch[_device] (the model Jacobian's products
-                                    with a vector) */
+                                    with a vector)
+                                    (added within 9, nothing else changed: mcalf_loglike_hvp_batch[_device], the product of
+                                    logL's exact Hessian with a vector) */
 
 enum {
     MCALF_OK = 0,
@@ -336,6 +339,27 @@ int mcalf_model_vjp_batch(mcalf_ctx* ctx, const double* P, const double* Q, int6
  * batch they allocate and synchronise nothing. */
 int mcalf_model_jvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* ddM, void* stream);
 int mcalf_model_vjp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dQ, int64_t batch, double* dG, void* stream);
+
+/* The product of logL's exact Hessian with a vector: HV[i, :] = (d2 logL[i] / dtheta2)(P[i]) V[i, :] under the context's
+ * conv_mode, P, V, HV all batch x ndim, row-major.  With r = d - m, W = 1/err^2 on the pixels nansum keeps (0 elsewhere) and
+ * J the model Jacobian,  H v = -J^T W (J v) + sum_i W_i r_i (d2 m_i / dtheta2) v : the Gauss-Newton (Fisher) term AND the
+ * curvature term, the directional derivative along v of the whole gradient mcalf_loglike_grad_batch computes.  Neither H
+ * nor J is formed.  The conventions are that entry's:
+ *   - ONE tangent per row: the batch axis is the vector axis, so k vectors at one theta are k rows that repeat it (the dense
+ *     Hessian is ndim rows with the identity's rows as tangents);
+ *   - the ncomp slot and the (N, z, b) of every component at or beyond the row's active count: those entries of V are
+ *     ignored (never read) and those of HV are exactly 0; likewise R / the continuum when the context fixes them, and R when
+ *     R <= velstep on the numpy path (no convolution);
+ *   - on the numpy path the LSF tap count is held at its value for the row;
+ *   - rows whose logL is -inf (asymmetric veto) or NaN, or whose tap count exceeds what the context provisions (R beyond
+ *     specres_max), get an all-NaN row; logL for that rule comes from the likelihood's own launch;
+ *   - a row's result does not depend on its batch, its position, the pass it falls in or the device count (no atomics,
+ *     every reduction in a fixed order).
+ * Host pointers, synchronous; a multi-device context cuts the batch into contiguous row blocks exactly as the gradient does. */
+int mcalf_loglike_hvp_batch(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* HV);
+/* Same, device pointers, on the caller's stream (single-device contexts); dP and dV are only read.  After one call of the
+ * same or a larger batch it allocates and synchronises nothing. */
+int mcalf_loglike_hvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dHV, void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

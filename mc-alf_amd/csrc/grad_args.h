@@ -1,4 +1,4 @@
-// What the gradient and Jacobian-product kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
+// What the gradient, Jacobian-product and Hessian-product kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
 // workspace layout and the kernel entry points.  Plain C++ -- host_grad.cpp is compiled without the HIP language mode.
 // Not part of the kernel-source hash (mc-alf_amd/build.py): the fused kernel does not include it.
 #pragma once
@@ -31,6 +31,10 @@ struct GradArgs {
     // T = -F dtau in `q`; the VJP points `q` at the caller's cotangent rows, which no kernel of its pass writes.
     const double* V;          // JVP: tangent rows of this pass [nrows, ndim]
     double* dM;               // JVP: directional derivative of the model [nrows, npix]
+    // the Hessian-vector product of logL (appended likewise).  Its pass keeps F and T = dF in `F` / `q` (jvp_forward), then
+    // g and dg in their place; the weighted residual and its tangent need two workspaces of their own.
+    double* ddtaps;           // HVP: d2 w_k / dR2 of the normalised taps [nrows, tapcap]
+    double *hq, *hdq;         // HVP: q = W (d - m) and dq = -W dM [nrows, npix]
 };
 
 // grad_kernels.hip; every kernel takes (const GradArgs a), grid as stated
@@ -44,6 +48,10 @@ MCALF_INTERNAL const void* vjp_model_kernel_ptr();       // grid = (ntiles, nrow
 MCALF_INTERNAL const void* vjp_finalize_kernel_ptr();    // as finalize, without the logL veto rule
 MCALF_INTERNAL const void* jvp_forward_kernel_ptr();     // grid = (ntiles, nrows): F = exp(-tau), T = -F dtau along the row's tangent
 MCALF_INTERNAL const void* jvp_model_kernel_ptr();       // grid = (ntiles, nrows): dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F)
+MCALF_INTERNAL const void* hvp_taps_kernel_ptr();        // grid = nrows: d2 w_k / dR2 of the taps the setup kernel left
+MCALF_INTERNAL const void* hvp_model_kernel_ptr();       // grid = (ntiles, nrows): q, dq; continuum and R partials of H v
+MCALF_INTERNAL const void* hvp_adjoint_kernel_ptr();     // grid = (ntiles, nrows): g and dg (in place of F and T)
+MCALF_INTERNAL const void* hvp_deriv_kernel_ptr();       // grid = (ntiles, nrows): (N, z, b) partials of H v, second-order Voigt pass
 MCALF_INTERNAL const void* grad_hjert_kernel_ptr();      // (const double* x, const double* y, long n, double* out): out[3i..] = H, H_x, H_y
 
 }  // namespace mcalf

@@ -26,6 +26,7 @@
 //   J^T q (VJP)  the gradient's own pass with the caller's cotangent in place of w (d - m): setup, forward, vjp_model (the
 //                continuum and R partials; the q workspace pointer IS the caller's Q), adjoint, deriv, vjp_finalize (no
 //                logL, so no veto rule: only rows whose tap count exceeds the cap are NaN)
+// and the product of logL's exact Hessian with a vector (mcalf_loglike_hvp_batch): see the hvp kernels below.
 #include <hip/hip_runtime.h>
 
 #include "grad_args.h"
@@ -429,6 +430,228 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_model_kernel(const GradA
     out[i] = ri.cont * cT + vc * cF + vR * ri.cont * dF;
 }
 
+// ---- The Hessian-vector product of logL (mcalf_loglike_hvp_batch): forward mode over the gradient's reverse pass. ----
+// With d(.) the directional derivative along the row's tangent v, T = dF (jvp_forward) and dM = d m (jvp_model's sum):
+//     q = W (d - m),  dq = -W dM                                          (W = 1/err^2 on the pixels nansum keeps, else 0)
+//     (H v)_cont = sum_i [dq L(F) + q (L(T) + v_R (dL/dR) F)]
+//     (H v)_R    = sum_i [dq cont (dL/dR) F + q v_cont (dL/dR) F + q cont ((dL/dR) T + v_R (d2L/dR2) F)]
+//     g = -F cont L^T q,   dg = -T cont L^T q - F v_cont L^T q - F cont v_R (dL/dR)^T q - F cont L^T dq
+//     (H v)_k    = sum_i [dg_i dtau_i/dtheta_k + g_i sum_k' d2tau_i/dtheta_k dtheta_k' v_k']      k, k' the (N, z, b) of ONE component
+// Per (component, line), s = nu/dnu (du/dz), z = u + i a ~ 1/b:
+//     d2tau/dN dtheta = ln10 dtau/dtheta,   d2tau/dz2 = K s^2 Re w'',   d2tau/dz db = -(K s/b) Re (z w)'',   d2tau/db2 = (K/b^2) Re (z^2 w)''
+// A pass: setup, hvp_taps, jvp_forward, hvp_model, hvp_adjoint, hvp_deriv, grad_finalize (the gradient's own, veto rule included).
+// The entries of v that are 0 columns of the gradient are never read; R's is not read either when the row has no taps (R <= velstep).
+
+namespace {
+
+struct RowTangent { double vR, vc; };
+
+__device__ __forceinline__ RowTangent row_tangent(const GradArgs& a, int r, const RowInfo& ri) {
+    const double* v = a.V + (size_t)r * a.ndim;
+    RowTangent o;
+    o.vR = (a.freespecres && (a.jax || ri.n > 0)) ? v[0] : 0.0;
+    o.vc = a.freecont ? v[a.freespecres ? 1 : 0] : 0.0;
+    return o;
+}
+
+}  // namespace
+
+// d2 w_k / dR2 of the normalised taps: with c_k = k^2 - sum_j w_j j^2 and var = sum_j w_j c_j^2,
+//     d2 w_k / dsigma2 = w_k ((c_k^2 - var) / sigma^6 - 3 c_k / sigma^4),   dsigma/dR constant.
+__global__ __launch_bounds__(kGradBlock) void mcalf_hvp_taps_kernel(const GradArgs a) {
+    __shared__ double lds[kGradBlock];
+    const int r = blockIdx.x;
+    const int t = threadIdx.x;
+    const RowInfo ri = row_info(a, r);
+    const int n = ri.n;
+    const double* taps = a.taps + (size_t)r * a.tapcap;
+    double* ddtaps = a.ddtaps + (size_t)r * a.tapcap;
+    const double sigma = (ri.R / kFwhmToSigma) / a.velstep;
+    double m2 = 0.0;
+    for (int k = t; k <= 2 * n; k += kGradBlock) {
+        const double dk = (double)(k - n);
+        m2 += taps[k] * dk * dk;
+    }
+    m2 = block_sum(m2, lds);
+    double var = 0.0;
+    for (int k = t; k <= 2 * n; k += kGradBlock) {
+        const double dk = (double)(k - n);
+        const double c = dk * dk - m2;
+        var += taps[k] * c * c;
+    }
+    var = block_sum(var, lds);
+    const double s2 = sigma * sigma, is4 = 1.0 / (s2 * s2), is6 = is4 / s2;
+    const double dsdR = 1.0 / (kFwhmToSigma * a.velstep);
+    for (int k = t; k <= 2 * n; k += kGradBlock) {
+        const double dk = (double)(k - n);
+        const double c = dk * dk - m2;
+        ddtaps[k] = (!a.jax && n == 0) ? 0.0 : taps[k] * ((c * c - var) * is6 - 3.0 * c * is4) * (dsdR * dsdR);
+    }
+}
+
+// q, dq and the continuum / R partials of H v: ONE tap loop gives L(F), (dL/dR) F, (d2L/dR2) F, L(T), (dL/dR) T.
+__global__ __launch_bounds__(kGradBlock) void mcalf_hvp_model_kernel(const GradArgs a) {
+    __shared__ double lds[kGradBlock];
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * kGradBlock + threadIdx.x;
+    const RowInfo ri = row_info(a, r);
+    const RowTangent rt = row_tangent(a, r, ri);
+    const double* F = a.F + (size_t)r * a.npix;
+    const double* T = a.q + (size_t)r * a.npix;
+    const double* taps = a.taps + (size_t)r * a.tapcap;
+    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
+    const double* ddtaps = a.ddtaps + (size_t)r * a.tapcap;
+    double pc = 0.0, pR = 0.0;
+    if (i < a.npix) {
+        double cF, cT, rF = 0.0, rT = 0.0, rrF = 0.0;
+        if (a.jax) {
+            const int h = ri.n;
+            if (i < h || i >= a.npix - h) {
+                cF = F[i]; cT = T[i];                                              // edge reset
+            } else {
+                double c = 0.0, d = 0.0, dd = 0.0, ct = 0.0, dt = 0.0;
+                for (int k = 0; k <= 2 * h; ++k) {
+                    const double f = F[i + k - h], tt = T[i + k - h];
+                    c += taps[k] * f;
+                    d += dtaps[k] * f;
+                    dd += ddtaps[k] * f;
+                    ct += taps[k] * tt;
+                    dt += dtaps[k] * tt;
+                }
+                cF = c; rF = d; rrF = dd; cT = ct; rT = dt;
+            }
+        } else if (ri.n > 0) {
+            const int n = ri.n;
+            int j = (int)(((long)i - n) % a.npix);
+            if (j < 0) j += a.npix;
+            double c = 0.0, d = 0.0, dd = 0.0, ct = 0.0, dt = 0.0;
+            for (int k = 0; k <= 2 * n; ++k) {                                     // periodic boundary
+                const double f = F[j], tt = T[j];
+                c += taps[k] * f;
+                d += dtaps[k] * f;
+                dd += ddtaps[k] * f;
+                ct += taps[k] * tt;
+                dt += dtaps[k] * tt;
+                if (++j == a.npix) j = 0;
+            }
+            cF = c / ri.bot; rF = d / ri.bot; rrF = dd / ri.bot; cT = ct / ri.bot; rT = dt / ri.bot;
+        } else {
+            cF = F[i]; cT = T[i];                                                  // R <= velstep: no convolution
+        }
+        const double is2 = a.ispec2[i];
+        const double res = a.obj[i] - ri.cont * cF;
+        const double term = is2 * res * res - a.lgis[i];
+        const bool drop = isnan(term);                                             // the pixels nansum drops: W = 0
+        const double dM = ri.cont * cT + rt.vc * cF + rt.vR * ri.cont * rF;
+        const double qv = drop ? 0.0 : is2 * res;
+        const double dqv = drop ? 0.0 : -is2 * dM;
+        a.hq[(size_t)r * a.npix + i] = qv;
+        a.hdq[(size_t)r * a.npix + i] = dqv;
+        pc = dqv * cF + qv * (cT + rt.vR * rF);
+        pR = (dqv * ri.cont + qv * rt.vc) * rF + qv * ri.cont * (rT + rt.vR * rrF);
+    }
+    pc = block_sum(pc, lds);
+    pR = block_sum(pR, lds);
+    if (threadIdx.x == 0) {
+        double* out = a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
+        if (a.freespecres) out[0] = (a.jax || ri.n > 0) ? pR : 0.0;
+        if (a.freecont) out[a.freespecres ? 1 : 0] = pc;
+        out[a.startind] = 0.0;                                                     // the ncomp slot
+    }
+}
+
+// g and dg in place of F and T: ONE tap loop gives L^T q, (dL/dR)^T q, L^T dq.
+__global__ __launch_bounds__(kGradBlock) void mcalf_hvp_adjoint_kernel(const GradArgs a) {
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * kGradBlock + threadIdx.x;
+    if (i >= a.npix) return;
+    const RowInfo ri = row_info(a, r);
+    const RowTangent rt = row_tangent(a, r, ri);
+    const double* q = a.hq + (size_t)r * a.npix;
+    const double* dq = a.hdq + (size_t)r * a.npix;
+    const double* taps = a.taps + (size_t)r * a.tapcap;
+    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
+    double lq, rq = 0.0, ldq;
+    if (a.jax) {
+        const int h = ri.n;
+        const bool edge = i < h || i >= a.npix - h;
+        lq = edge ? q[i] : 0.0;
+        ldq = edge ? dq[i] : 0.0;
+        // interior outputs o = i - k + h with tap k read pixel i
+        const int klo = max(0, i + 2 * h - a.npix + 1), khi = min(2 * h, i);
+        for (int k = klo; k <= khi; ++k) {
+            const double qo = q[i - k + h];
+            lq += taps[k] * qo;
+            rq += dtaps[k] * qo;
+            ldq += taps[k] * dq[i - k + h];
+        }
+    } else if (ri.n > 0) {
+        const int n = ri.n;
+        int j = (int)(((long)i + n) % a.npix);
+        double c = 0.0, d = 0.0, cd = 0.0;
+        for (int k = 0; k <= 2 * n; ++k) {                                         // output j read pixel i through tap k
+            const double qo = q[j];
+            c += taps[k] * qo;
+            d += dtaps[k] * qo;
+            cd += taps[k] * dq[j];
+            if (--j < 0) j = a.npix - 1;
+        }
+        lq = c / ri.bot; rq = d / ri.bot; ldq = cd / ri.bot;
+    } else {
+        lq = q[i]; ldq = dq[i];
+    }
+    double* F = a.F + (size_t)r * a.npix;
+    double* T = a.q + (size_t)r * a.npix;
+    const double f = F[i], tt = T[i];
+    F[i] = -f * ri.cont * lq;
+    T[i] = -(tt * ri.cont + f * rt.vc) * lq - f * ri.cont * (rt.vR * rq + ldq);
+}
+
+// The second-order Voigt pass: per active component the three sums of dg dtau/dtheta_k + g (d2tau/dtheta_k dtheta_k') v_k'.
+__global__ __launch_bounds__(kGradBlock) void mcalf_hvp_deriv_kernel(const GradArgs a) {
+    __shared__ double lds[3 * kGradBlock];
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * kGradBlock + threadIdx.x;
+    const RowInfo ri = row_info(a, r);
+    const bool valid = i < a.npix;
+    const double g = valid ? a.F[(size_t)r * a.npix + i] : 0.0;
+    const double dg = valid ? a.q[(size_t)r * a.npix + i] : 0.0;
+    const double nu = valid ? a.nu[i] : a.nu[0];
+    const double* v = a.V + (size_t)r * a.ndim;
+    double* out = a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
+    const int ncomp = ri.nc + a.nfill;                 // active targets, then the fillers
+    for (int c = 0; c < ncomp; ++c) {
+        const bool fill = c >= ri.nc;
+        const int slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
+        const int nl = fill ? 1 : a.nlines;
+        const int col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
+        double tN = 0.0, tz = 0.0, tb = 0.0, tzz = 0.0, tzb = 0.0, tbb = 0.0;
+        for (int l = 0; l < nl; ++l) {
+            const double* rec = rec_of(a, r, slot0 + l);
+            const double u = nu * rec[0] - rec[1], y = rec[2], K = rec[3], s = nu * rec[4], ib = rec[5];
+            double wr, dr, e, d2, e2, e3;
+            faddeeva_d2w(u, y, wr, dr, e, d2, e2, e3);
+            tN += K * wr;                                   // tau
+            tz += K * dr * s;                               // K H_u du/dz
+            tb -= K * ib * e;                               // -(K/b) Re (z w)'
+            tzz += K * s * s * d2;
+            tzb -= K * s * ib * e2;
+            tbb += K * ib * ib * e3;
+        }
+        const double vN = kLn10 * v[col], vz = v[col + 1], vb = v[col + 2];
+        double sN = kLn10 * (dg * tN + g * (tN * vN + tz * vz + tb * vb));
+        double sz = dg * tz + g * (tz * vN + tzz * vz + tzb * vb);
+        double sb = dg * tb + g * (tb * vN + tzb * vz + tbb * vb);
+        block_sum3(sN, sz, sb, lds);
+        if (threadIdx.x == 0) { out[col] = sN; out[col + 1] = sz; out[col + 2] = sb; }
+    }
+    if (threadIdx.x == 0)
+        for (int c = ri.nc; c < a.ncompmax; ++c) {     // inactive components: exactly 0
+            const int col = 1 + 3 * c + a.startind;
+            out[col] = out[col + 1] = out[col + 2] = 0.0;
+        }
+}
+
 __global__ void mcalf_grad_hjert_kernel(const double* x, const double* y, long n, double* out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -450,5 +673,9 @@ const void* vjp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf
 const void* vjp_finalize_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_vjp_finalize_kernel); }
 const void* jvp_forward_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_jvp_forward_kernel); }
 const void* jvp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_jvp_model_kernel); }
+const void* hvp_taps_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_taps_kernel); }
+const void* hvp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_model_kernel); }
+const void* hvp_adjoint_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_adjoint_kernel); }
+const void* hvp_deriv_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_deriv_kernel); }
 const void* grad_hjert_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_hjert_kernel); }
 }  // namespace mcalf

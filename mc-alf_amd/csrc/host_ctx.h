@@ -268,6 +268,9 @@ struct mcalf_ctx {
     double *g_P = nullptr, *g_logL = nullptr, *g_G = nullptr, *g_X = nullptr;
     size_t cap_g_rows = 0, cap_g_recs = 0, cap_g_taps = 0, cap_g_dtaps = 0, cap_g_F = 0, cap_g_q = 0, cap_g_part = 0;
     size_t cap_g_P = 0, cap_g_logL = 0, cap_g_G = 0, cap_g_X = 0;
+    // The Hessian-vector product's own: the taps' second R derivative, q and dq of a pass, the tangent rows of the host entry
+    double *g_ddtaps = nullptr, *g_hq = nullptr, *g_hdq = nullptr, *g_V = nullptr;
+    size_t cap_g_ddtaps = 0, cap_g_hq = 0, cap_g_hdq = 0, cap_g_V = 0;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).

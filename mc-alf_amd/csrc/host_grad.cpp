@@ -2,7 +2,8 @@
 // mcalf_voigt_hjerting_grad.  logL itself comes from the likelihood's own launch (host_abi.cpp: launch), so the two
 // entries agree on it bit for bit; the gradient kernels then run over row blocks whose per-row workspaces stay within
 // kGradChunkBytes.  The model Jacobian's products with a vector, mcalf_model_jvp_batch[_device] and
-// mcalf_model_vjp_batch[_device], run over the same row blocks and workspaces.
+// mcalf_model_vjp_batch[_device], run over the same row blocks and workspaces.  The Hessian-vector product of logL,
+// mcalf_loglike_hvp_batch[_device], shares them too and adds three per-row workspaces, so its passes are cut smaller.
 #include <cmath>
 
 #include "grad_args.h"
@@ -22,9 +23,11 @@ int grad_tapcap(const mcalf_ctx* ctx) { return 2 * grad_ncap(ctx) + 1; }
 // the pixel kernels carry the row on grid.y (a short spectrum's rows are ~2 KB each, so the byte bound alone would
 // allow ~200 000 of them), the same cap as the likelihood's wide path (host_abi.cpp: wide_rows_per_pass).
 constexpr int64_t kGradMaxRows = 65535;
-int64_t grad_chunk_rows(const mcalf_ctx* ctx) {
-    const int64_t per_row = (2 * (int64_t)ctx->npix + 2 * (int64_t)grad_tapcap(ctx) + kGradRow +
-                             (int64_t)grad_nslots(ctx) * kGradRec + (int64_t)grad_ntiles(ctx) * ctx->ndim) * (int64_t)sizeof(double);
+// An HVP pass (`hvp`) also holds q, dq and the taps' second R derivative per row; the other entries' passes stay as they were.
+int64_t grad_chunk_rows(const mcalf_ctx* ctx, bool hvp = false) {
+    int64_t per_row = (2 * (int64_t)ctx->npix + 2 * (int64_t)grad_tapcap(ctx) + kGradRow +
+                       (int64_t)grad_nslots(ctx) * kGradRec + (int64_t)grad_ntiles(ctx) * ctx->ndim) * (int64_t)sizeof(double);
+    if (hvp) per_row += (2 * (int64_t)ctx->npix + (int64_t)grad_tapcap(ctx)) * (int64_t)sizeof(double);
     return std::min<int64_t>(kGradMaxRows, std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row));
 }
 
@@ -42,12 +45,25 @@ int grad_prepare(mcalf_ctx* ctx, int64_t batch, bool own_q = true) {
     return grow(ctx, &ctx->g_part, &ctx->cap_g_part, rows * grad_ntiles(ctx) * ctx->ndim);
 }
 
+// The HVP's pass: the shared workspaces for its (smaller) row count, q, dq, the taps' second derivative, and logL of the batch.
+int hvp_prepare(mcalf_ctx* ctx, int64_t batch) {
+    const int64_t rows64 = std::min<int64_t>(batch, grad_chunk_rows(ctx, true));
+    const size_t rows = (size_t)rows64;
+    int rc;
+    if ((rc = grad_prepare(ctx, rows64))) return rc;
+    if ((rc = grow(ctx, &ctx->g_ddtaps, &ctx->cap_g_ddtaps, rows * grad_tapcap(ctx)))) return rc;
+    if ((rc = grow(ctx, &ctx->g_hq, &ctx->cap_g_hq, rows * ctx->npix))) return rc;
+    if ((rc = grow(ctx, &ctx->g_hdq, &ctx->cap_g_hdq, rows * ctx->npix))) return rc;
+    return grow(ctx, &ctx->g_logL, &ctx->cap_g_logL, (size_t)batch);
+}
+
 // What every pass of a batch shares; the row pointers and the row count are set per pass.
 GradArgs grad_args(const mcalf_ctx* ctx) {
     GradArgs a = {};
     a.nu = ctx->d_nu; a.obj = ctx->d_obj; a.ispec2 = ctx->d_ispec2; a.lgis = ctx->d_lgis; a.lines = ctx->d_lines;
     a.rows = ctx->g_rows; a.recs = ctx->g_recs; a.taps = ctx->g_taps; a.dtaps = ctx->g_dtaps;
     a.F = ctx->g_F; a.q = ctx->g_q; a.part = ctx->g_part;
+    a.ddtaps = ctx->g_ddtaps; a.hq = ctx->g_hq; a.hdq = ctx->g_hdq;
     a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = grad_ntiles(ctx); a.tapcap = grad_tapcap(ctx); a.nslots = grad_nslots(ctx);
     a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax; a.nfill = ctx->nfill; a.startind = ctx->startind; a.endind = ctx->endind;
     a.freespecres = ctx->freespecres; a.freecont = ctx->freecont; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0;
@@ -133,6 +149,36 @@ int vjp_launch(mcalf_ctx* ctx, const double* dP, const double* dQ, int64_t batch
     return MCALF_OK;
 }
 
+// HV = (d2 logL / dtheta2)(P) V row by row.  logL of the batch (for the veto rule) comes from the likelihood's launch into the
+// context's own g_logL; then per pass setup, the taps' second derivative, the tangent Voigt pass, q / dq, g / dg, the
+// second-order Voigt pass and the gradient's finalize.
+int hvp_launch(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dHV, hipStream_t stream) {
+    if (batch <= 0) return MCALF_OK;
+    int rc = hvp_prepare(ctx, batch);
+    if (rc) return rc;
+    if ((rc = launch(ctx, kModeLogL, dP, batch, 0, 0, ctx->g_logL, nullptr, stream))) return rc;
+    GradArgs a = grad_args(ctx);
+    const int64_t chunk = grad_chunk_rows(ctx, true);
+    for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
+        a.P = dP + (size_t)row0 * ctx->ndim;
+        a.V = dV + (size_t)row0 * ctx->ndim;
+        a.logL = ctx->g_logL + row0;
+        a.G = dHV + (size_t)row0 * ctx->ndim;
+        a.nrows = (int)std::min(chunk, batch - row0);
+        const dim3 px((unsigned)a.ntiles, (unsigned)a.nrows), row((unsigned)a.nrows);
+        const int64_t cells = (int64_t)a.nrows * a.ndim;
+        if ((rc = grad_kernel(ctx, grad_setup_kernel_ptr(), row, a, stream))) return rc;
+        if ((rc = grad_kernel(ctx, hvp_taps_kernel_ptr(), row, a, stream))) return rc;
+        if ((rc = grad_kernel(ctx, jvp_forward_kernel_ptr(), px, a, stream))) return rc;
+        if ((rc = grad_kernel(ctx, hvp_model_kernel_ptr(), px, a, stream))) return rc;
+        if ((rc = grad_kernel(ctx, hvp_adjoint_kernel_ptr(), px, a, stream))) return rc;
+        if ((rc = grad_kernel(ctx, hvp_deriv_kernel_ptr(), px, a, stream))) return rc;
+        if ((rc = grad_kernel(ctx, grad_finalize_kernel_ptr(), dim3((unsigned)((cells + kGradBlock - 1) / kGradBlock)), a, stream)))
+            return rc;
+    }
+    return MCALF_OK;
+}
+
 // The host-pointer JVP (X = V [batch, ndim], Y = dM [batch, npix]) or VJP (X = Q [batch, npix], Y = G [batch, ndim]):
 // P and X to the device, the kernels, Y back, all on the context's stream; a multi-device context cuts the rows over
 // its devices.  g_G holds the [batch, ndim] operand (V in, or G out), g_X the [batch, npix] one.
@@ -180,7 +226,8 @@ int deriv_device(mcalf_ctx* ctx, bool jvp, const double* dP, const double* dX, i
 }  // namespace
 
 void grad_release(mcalf_ctx* ctx) {
-    double* bufs[] = {ctx->g_rows, ctx->g_recs, ctx->g_taps, ctx->g_dtaps, ctx->g_F, ctx->g_q, ctx->g_part, ctx->g_P, ctx->g_logL, ctx->g_G, ctx->g_X};
+    double* bufs[] = {ctx->g_rows, ctx->g_recs, ctx->g_taps, ctx->g_dtaps, ctx->g_F, ctx->g_q, ctx->g_part, ctx->g_P, ctx->g_logL, ctx->g_G, ctx->g_X,
+                      ctx->g_ddtaps, ctx->g_hq, ctx->g_hdq, ctx->g_V};
     for (double* b : bufs)
         if (b) (void)hipFree(b);
 }
@@ -236,6 +283,42 @@ extern "C" int mcalf_model_vjp_batch(mcalf_ctx* ctx, const double* P, const doub
 
 extern "C" int mcalf_model_vjp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dQ, int64_t batch, double* dG, void* stream) {
     return deriv_device(ctx, false, dP, dQ, batch, dG, stream);
+}
+
+extern "C" int mcalf_loglike_hvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dHV, void* stream) {
+    if (!ctx || batch < 0 || (batch > 0 && (!dP || !dV || !dHV))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
+    MCALF_SINGLE_ONLY(ctx, "mcalf_loglike_hvp_batch_device");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    return hvp_launch(ctx, dP, dV, batch, dHV, (hipStream_t)stream);
+}
+
+extern "C" int mcalf_loglike_hvp_batch(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* HV) {
+    if (!ctx || batch < 0 || (batch > 0 && (!P || !V || !HV))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
+    if (batch == 0) return MCALF_OK;
+    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, cut as the gradient's
+        struct HvpShard { const double *P, *V; double* HV; int ndim; } c = {P, V, HV, ctx->ndim};
+        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
+            const HvpShard* s = static_cast<const HvpShard*>(arg);
+            return mcalf_loglike_hvp_batch(static_cast<mcalf_ctx*>(sub), s->P + (size_t)lo * s->ndim, s->V + (size_t)lo * s->ndim, hi - lo,
+                                           s->HV + (size_t)lo * s->ndim);
+        }, &c);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t cells = (size_t)batch * ctx->ndim;
+    int rc;
+    if ((rc = grow(ctx, &ctx->g_P, &ctx->cap_g_P, cells))) return rc;
+    if ((rc = grow(ctx, &ctx->g_V, &ctx->cap_g_V, cells))) return rc;
+    if ((rc = grow(ctx, &ctx->g_G, &ctx->cap_g_G, cells))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_P, P, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_V, V, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = hvp_launch(ctx, ctx->g_P, ctx->g_V, batch, ctx->g_G, ctx->stream))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(HV, ctx->g_G, cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->last.path = MCALF_PATH_HOST_STAGED;
+    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
+    ctx->last.pinned_out = is_pinned_host(HV) ? 1 : 0;
+    return MCALF_OK;
 }
 
 extern "C" int mcalf_voigt_hjerting_grad(const double* x, const double* y, int64_t n, double* out, int32_t device) {

@@ -98,4 +98,56 @@ __device__ __forceinline__ void faddeeva_dw(double x, double y, double& wr, doub
     e = wr + (x * dr - y * di);
 }
 
+// Second order, for the Hessian-vector product of logL (mcalf_hvp_deriv_kernel).  With K H(u, a), u and a both ~ 1/b:
+//     d2tau/dz2 ~ Re w'',   d2tau/dz db ~ Re (z w)'' = Re (2 w' + z w''),   d2tau/db2 ~ Re (z^2 w)'' = Re (2 (z w)' + z (z w)'')
+// Outputs: wr = Re w, dr = Re w', e = Re (z w)' as faddeeva_dw gives them, d2 = Re w'', e2 = Re (z w)'', e3 = Re (z^2 w)''.
+//   |z| <  8 : algebraic from w and w':  w'' = -2 (w + z w'),  then the two identities above
+//   |z| >= 8 : every combination from its OWN series, differentiated term by term -- in a Lorentzian wing (z w)'' and
+//              (z^2 w)'' cancel to O(|z|^-2) and O(|z|^-4) of their O(1) terms, which leaves no digit of the algebraic form:
+//                  w''       = i/(sqrt(pi) z^3) sum_k (2k+1)(2k+2) c_k      (z w)''   = i/(sqrt(pi) z^2) sum_k 2k (2k+1) c_k
+//                  (z^2 w)'' = i/(sqrt(pi) z)   sum_k 2k (2k-1) c_k         c_k = (2k-1)!!/(2 z^2)^k
+//              two terms more than asym_terms: the second derivatives weigh the last term 2k times heavier than the first.
+__device__ __forceinline__ void faddeeva_d2w(double x, double y, double& wr, double& dr, double& e, double& d2, double& e2,
+                                             double& e3) {
+    const double r2 = x * x + y * y;
+    if (r2 >= kAsymR2) {
+        const double z2r = x * x - y * y, z2i = 2.0 * x * y;
+        const double rr2 = 1.0 / r2, rm2 = rr2 * rr2;
+        const double hr = 0.5 * z2r * rm2, hi = -0.5 * z2i * rm2;
+        double cr = 1.0, ci = 0.0, sr = 0.0, si = 0.0, tr = 0.0, ti = 0.0, er = 0.0, ei = 0.0;
+        double ur = 0.0, ui = 0.0, pr = 0.0, pi = 0.0, qr = 0.0, qi = 0.0;
+        const int nt = asym_terms(r2) + 2;
+        for (int k = 0; k < nt; ++k) {
+            const double f = (double)(2 * k + 1), g = (double)(2 * k);
+            sr += cr; si += ci;
+            tr -= f * cr; ti -= f * ci;
+            er -= g * cr; ei -= g * ci;
+            ur += f * (g + 2.0) * cr; ui += f * (g + 2.0) * ci;      // w''
+            pr += g * f * cr; pi += g * f * ci;                      // (z w)''
+            qr += g * (g - 1.0) * cr; qi += g * (g - 1.0) * ci;      // (z^2 w)''
+            const double nr = f * (cr * hr - ci * hi), ni = f * (cr * hi + ci * hr);
+            cr = nr; ci = ni;
+        }
+        // i/(sqrt(pi) z), i/(sqrt(pi) z^2) as in faddeeva_dw; i/(sqrt(pi) z^3) = (i/(sqrt(pi) z^2)) conj(z) / |z|^2
+        const double ar = y * kGradInvSqrtPi * rr2, ai = x * kGradInvSqrtPi * rr2;
+        const double br = z2i * kGradInvSqrtPi * rm2, bi = z2r * kGradInvSqrtPi * rm2;
+        const double gr = (br * x + bi * y) * rr2, gi = (bi * x - br * y) * rr2;
+        wr = ar * sr - ai * si;
+        e = ar * er - ai * ei;
+        e3 = ar * qr - ai * qi;
+        dr = br * tr - bi * ti;
+        e2 = br * pr - bi * pi;
+        d2 = gr * ur - gi * ui;
+        return;
+    }
+    double wi, di;
+    faddeeva_dw(x, y, wr, wi, dr, di, e);
+    const double Ei = wi + (x * di + y * dr);                      // Im (z w)'
+    const double d2i = -2.0 * Ei;
+    d2 = -2.0 * e;                                                 // w'' = -2 (z w)'
+    const double e2i = 2.0 * di + (x * d2i + y * d2);
+    e2 = 2.0 * dr + (x * d2 - y * d2i);                            // (z w)'' = 2 w' + z w''
+    e3 = 2.0 * e + (x * e2 - y * e2i);                             // (z^2 w)'' = 2 (z w)' + z (z w)''
+}
+
 }  // namespace mcalf

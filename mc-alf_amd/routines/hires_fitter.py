@@ -483,6 +483,32 @@ class als_fitter:
             w = np.where(np.isnan(w * np.asarray(self.obj, dtype=float) ** 2 - np.log(w)), 0.0, w)
         return self.model_vjp_batch(P, w * self.model_jvp_batch(P, V))
 
+    def loglike_hvp_batch(self, P, V, out=None):
+        """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's
+        `conv_mode` applied to one tangent per row ([batch, ndim] -> [batch, ndim]; HIP kernels, H is never formed).  It is
+        the directional derivative of `loglike_grad_batch`'s gradient along V[i]: the Fisher term -J^T W J v of
+        `fisher_matvec_batch` plus the curvature term sum_i W_i (d_i - m_i) (d2 m_i / dtheta2) v.
+
+        The conventions are `loglike_grad_batch`'s: the ncomp entry, the (N, z, b) of components at or beyond the row's
+        active count, the R / continuum entries the context fixes and R where R <= velstep (numpy path) are ignored in V
+        and exactly 0 in HV; the tap count of the numpy path is held at its value for the row; rows whose logL is -inf or
+        NaN, or whose R needs more taps than the context provisions, are all NaN.  `out` is filled in place when given."""
+        return self._deriv_call(self._lib.mcalf_loglike_hvp_batch, P, V, self.ndim, out, self.ndim, "V")
+
+    def lnlhood_hessp(self, p, v):
+        """H(p) v for one parameter vector and one tangent (`loglike_hvp_batch`).  Negated, it is the `hessp` of
+        `scipy.optimize.minimize(..., method="trust-ncg")` for the objective -lnlhood."""
+        self._check_scalar(p)
+        return self.loglike_hvp_batch(np.asarray(p, dtype=float).reshape(1, -1), np.asarray(v, dtype=float).reshape(1, -1))[0]
+
+    def lnlhood_hessian(self, p):
+        """The dense Hessian H[ndim, ndim] of logL at one parameter vector: one `loglike_hvp_batch` call of ndim rows that
+        repeat `p`, with the identity's rows as tangents.  A convenience: it costs ndim passes over the spectrum; for
+        products with a vector use `loglike_hvp_batch`, which never forms H.  Row k is H e_k; H is symmetric to rounding."""
+        self._check_scalar(p)
+        P = np.tile(np.asarray(p, dtype=float).reshape(1, -1), (self.ndim, 1))
+        return self.loglike_hvp_batch(P, np.eye(self.ndim))
+
     def model_jacobian(self, p):
         """J[npix, ndim] = d model / d theta at one parameter vector: one `model_jvp_batch` call of ndim rows that
         repeat `p`, with the identity's rows as tangents.  It costs ndim Voigt passes over the spectrum; for products

@@ -1,6 +1,7 @@
-"""Device-entry timing of the analytic gradient and of the model Jacobian's products: ms per step of
-mcalf_loglike_grad_batch_device, mcalf_model_jvp_batch_device, mcalf_model_vjp_batch_device and the Fisher product (one
-JVP, the weights, one VJP) next to mcalf_loglike_batch_device on the same rows (configs C and E by default), HIP events on
+"""Device-entry timing of the analytic gradient, of the model Jacobian's products and of the Hessian-vector product: ms per
+step of mcalf_loglike_grad_batch_device, mcalf_model_jvp_batch_device, mcalf_model_vjp_batch_device, the Fisher product (one
+JVP, the weights, one VJP) and mcalf_loglike_hvp_batch_device (also over two gradient steps, what a finite difference of
+the gradient costs) next to mcalf_loglike_batch_device on the same rows (configs C and E by default), HIP events on
 one stream, warm-up, median over `--steps` steps; one JSON line.  python tools/grad_timing.py [--configs C E] [--steps 20] [--warmup 3] [--batch N]"""
 import argparse
 import ctypes as C
@@ -82,14 +83,21 @@ def main():
                 dM.mul_(dW)
                 assert lib.mcalf_model_vjp_batch_device(ctx, dP.data_ptr(), dM.data_ptr(), batch, dG.data_ptr(), s) == 0
 
+            dHV = torch.empty_like(dG)
+
+            def hvp():
+                assert lib.mcalf_loglike_hvp_batch_device(ctx, dP.data_ptr(), dV.data_ptr(), batch, dHV.data_ptr(), s) == 0
+
             t_l = _time(logl, args.steps, args.warmup)
             t_g = _time(grad, args.steps, args.warmup)
             t_j = _time(jvp, args.steps, args.warmup)
             t_v = _time(vjp, args.steps, args.warmup)
             t_f = _time(fisher, args.steps, args.warmup)
+            t_h = _time(hvp, args.steps, args.warmup)
         out["configs"][name] = {"batch": batch, "npix": int(fit.obj.size), "ndim": int(P.shape[1]), "logl_ms": round(t_l, 4),
                                 "grad_ms": round(t_g, 4), "ratio": round(t_g / t_l, 3), "jvp_ms": round(t_j, 4),
-                                "vjp_ms": round(t_v, 4), "fisher_ms": round(t_f, 4), "jvp_over_grad": round(t_j / t_g, 3)}
+                                "vjp_ms": round(t_v, 4), "fisher_ms": round(t_f, 4), "jvp_over_grad": round(t_j / t_g, 3),
+                                "hvp_ms": round(t_h, 4), "hvp_over_two_grads": round(t_h / (2 * t_g), 3)}
     print(json.dumps(out))
 
 
