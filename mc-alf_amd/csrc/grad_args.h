@@ -1,5 +1,5 @@
-// What the gradient, Jacobian-product and Hessian-product kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
-// workspace layout and the kernel entry points.  Plain C++ -- host_grad.cpp is compiled without the HIP language mode.
+// What the derivative kernels (grad_kernels.hip) and their host side (host_grad.cpp) share: the argument block, the
+// workspace layout and the kernel handles.  Plain C++ -- host_grad.cpp is compiled without the HIP language mode.
 // Not part of the kernel-source hash (mc-alf_amd/build.py): the fused kernel does not include it.
 #pragma once
 #include <cstddef>
@@ -27,31 +27,39 @@ struct GradArgs {
     int nrows, npix, ndim, ntiles, tapcap, nslots;
     int nlines, ncompmax, nfill, startind, endind, freespecres, freecont, jax, jax_half, n_cap;
     double specres_fixed, contval_fixed, velstep;
-    // the model Jacobian's products (appended: the gradient kernels' argument offsets stay as they were).  The JVP keeps
-    // T = -F dtau in `q`; the VJP points `q` at the caller's cotangent rows, which no kernel of its pass writes.
-    const double* V;          // JVP: tangent rows of this pass [nrows, ndim]
+    // The JVP and the HVP keep T = dF in `q`; the VJP points `q` at the caller's cotangent rows, which no kernel of its pass writes.
+    const double* V;          // JVP, HVP: tangent rows of this pass [nrows, ndim]
     double* dM;               // JVP: directional derivative of the model [nrows, npix]
-    // the Hessian-vector product of logL (appended likewise).  Its pass keeps F and T = dF in `F` / `q` (jvp_forward), then
-    // g and dg in their place; the weighted residual and its tangent need two workspaces of their own.
     double* ddtaps;           // HVP: d2 w_k / dR2 of the normalised taps [nrows, tapcap]
-    double *hq, *hdq;         // HVP: q = W (d - m) and dq = -W dM [nrows, npix]
+    double *hq, *hdq;         // HVP: q = W (d - m) and dq = -W dM [nrows, npix] (F and q hold g and dg after its adjoint kernel)
 };
 
-// grad_kernels.hip; every kernel takes (const GradArgs a), grid as stated
-MCALF_INTERNAL const void* grad_setup_kernel_ptr();      // grid = nrows: decode, records, taps
-MCALF_INTERNAL const void* grad_forward_kernel_ptr();    // grid = (ntiles, nrows): F = exp(-tau)
-MCALF_INTERNAL const void* grad_model_kernel_ptr();      // grid = (ntiles, nrows): q, continuum and R partials
-MCALF_INTERNAL const void* grad_adjoint_kernel_ptr();    // grid = (ntiles, nrows): g = -F cont L^T q (in place of F)
-MCALF_INTERNAL const void* grad_deriv_kernel_ptr();      // grid = (ntiles, nrows): (N, z, b) partials
-MCALF_INTERNAL const void* grad_finalize_kernel_ptr();   // grid = ceil(nrows * ndim / kGradBlock): tiles summed in order
-MCALF_INTERNAL const void* vjp_model_kernel_ptr();       // grid = (ntiles, nrows): the model kernel with q = the caller's cotangent
-MCALF_INTERNAL const void* vjp_finalize_kernel_ptr();    // as finalize, without the logL veto rule
-MCALF_INTERNAL const void* jvp_forward_kernel_ptr();     // grid = (ntiles, nrows): F = exp(-tau), T = -F dtau along the row's tangent
-MCALF_INTERNAL const void* jvp_model_kernel_ptr();       // grid = (ntiles, nrows): dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F)
-MCALF_INTERNAL const void* hvp_taps_kernel_ptr();        // grid = nrows: d2 w_k / dR2 of the taps the setup kernel left
-MCALF_INTERNAL const void* hvp_model_kernel_ptr();       // grid = (ntiles, nrows): q, dq; continuum and R partials of H v
-MCALF_INTERNAL const void* hvp_adjoint_kernel_ptr();     // grid = (ntiles, nrows): g and dg (in place of F and T)
-MCALF_INTERNAL const void* hvp_deriv_kernel_ptr();       // grid = (ntiles, nrows): (N, z, b) partials of H v, second-order Voigt pass
-MCALF_INTERNAL const void* grad_hjert_kernel_ptr();      // (const double* x, const double* y, long n, double* out): out[3i..] = H, H_x, H_y
+// The kernels of grad_kernels.hip.  All but the last take (const GradArgs a) and kGradBlock threads per workgroup; the enum is
+// ordered by grid, which host_grad.cpp derives from the handle alone.
+enum GradKernel {
+    // grid = nrows: one workgroup per row
+    kGradSetup,          // decode, (component, line) records, normalised taps and their R derivative
+    kGradHvpTaps,        // d2 w_k / dR2 of the taps the setup kernel left
+    // grid = (ntiles, nrows): one pixel per thread
+    kGradFirstPixel,
+    kGradForward = kGradFirstPixel,   // F = exp(-tau)
+    kGradModel,          // q = w (d - m); continuum and R partials
+    kGradVjpModel,       // the model kernel with q = the caller's cotangent
+    kGradAdjoint,        // g = -F cont L^T q (in place of F)
+    kGradDeriv,          // (N, z, b) partials
+    kGradJvpForward,     // F = exp(-tau), T = -F dtau along the row's tangent (in q)
+    kGradJvpModel,       // dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F)
+    kGradHvpModel,       // q, dq (hq, hdq); continuum and R partials of H v
+    kGradHvpAdjoint,     // g and dg (in place of F and T)
+    kGradHvpDeriv,       // (N, z, b) partials of H v, the second-order Voigt pass
+    // grid = ceil(nrows * ndim / kGradBlock): one cell of G per thread
+    kGradFirstCell,
+    kGradFinalize = kGradFirstCell,   // tiles summed in order; -inf / NaN logL rows and rows beyond the tap cap get NaN
+    kGradVjpFinalize,    // as finalize, without the logL veto rule
+    // (const double* x, const double* y, long n, double* out), 256 threads per point block: out[3i..] = H, H_x, H_y
+    kGradHjert,
+    kGradKernelCount
+};
+MCALF_INTERNAL const void* grad_kernel_ptr(GradKernel k);
 
 }  // namespace mcalf

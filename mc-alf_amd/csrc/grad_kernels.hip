@@ -1,4 +1,6 @@
-// The analytic gradient of logL (mcalf_loglike_grad_batch, host_grad.cpp) for gfx950, float64.
+// The derivative kernels for gfx950, float64: the analytic gradient of logL (mcalf_loglike_grad_batch), the model Jacobian's
+// products with a vector (mcalf_model_jvp_batch / _vjp_batch) and the product of logL's exact Hessian with a vector
+// (mcalf_loglike_hvp_batch).  host_grad.cpp holds the kernel sequence of each product.
 //
 // With w = 1/err^2, m = cont L(F), F = exp(-sum tau) and q_i = w_i (d_i - m_i) (0 on the pixels nansum drops):
 //     dlogL/dtheta = sum_i q_i dm_i/dtheta
@@ -7,26 +9,23 @@
 // L is the context's convolution: the periodic one with the astropy tap count on the numpy path (none when R <= velstep),
 // the fixed grid with the edge reset on the JAX path; L^T is its transpose.  Per (component, line), K = cne/dnu:
 //     dtau/dN = ln10 tau,   dtau/dz = K H_u (c/lambda)/dnu,   dtau/db = -(K/b)(H + u H_u + a H_a)
+// J v (JVP), J = dm/dtheta: dtau = sum_c (ln10 tau_c v_N + K H_u (nu/dnu) v_z - (K/b) e v_b), T = -F dtau,
+//     dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F).
+// J^T q (VJP): the gradient with the caller's cotangent in place of w (d - m) (the q pointer IS the caller's array) and no
+//     logL, so no veto rule: only rows whose tap count exceeds the cap are NaN.
+// H v (HVP): see the comment above the hvp kernels.
 //
-// Six kernels per pass over a block of rows, every reduction in a fixed order (no atomics): a row's bits do not depend
-// on its batch, its pass or its device.
-//   setup    one workgroup per row: decode, (component, line) records, normalised taps and their R derivative
-//   forward  (tile, row): F = exp(-tau)                                  -> F workspace
-//   model    (tile, row): m = cont L(F), q; continuum and R partials     -> q workspace, partials
-//   adjoint  (tile, row): g = -F cont (L^T q)_i                          -> F workspace (in place)
-//   deriv    (tile, row): H, H_u, H_a of every active (component, line); per component the three weighted sums
-//   finalize (row, column): partials summed over tiles in order; -inf / NaN logL rows get NaN
-// The convolutions read the workspace in HBM, so any LSF width the likelihood accepts works.
-//
-// The same file holds the model Jacobian's two products with a vector (mcalf_model_jvp_batch / _vjp_batch), J = dm/dtheta:
-//   J v   (JVP)  setup, then
-//     jvp_forward (tile, row): ONE Voigt pass: tau and dtau = sum_c (ln10 tau_c v_N + K H_u (nu/dnu) v_z - (K/b) e v_b),
-//                              F = exp(-tau) -> F workspace, T = -F dtau -> q workspace
-//     jvp_model   (tile, row): dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F), one tap loop over F and T
-//   J^T q (VJP)  the gradient's own pass with the caller's cotangent in place of w (d - m): setup, forward, vjp_model (the
-//                continuum and R partials; the q workspace pointer IS the caller's Q), adjoint, deriv, vjp_finalize (no
-//                logL, so no veto rule: only rows whose tap count exceeds the cap are NaN)
-// and the product of logL's exact Hessian with a vector (mcalf_loglike_hvp_batch): see the hvp kernels below.
+// What every kernel shares, each written once:
+//   lsf_forward<kWhat>   one walk over a pixel's taps: L F, (dL/dR) F, (d2L/dR2) F, L T, (dL/dR) T as the template asks;
+//                        the JAX edge reset, the periodic wrap with the division by bot, the pass-through of a row without taps
+//   lsf_transposed<kTan> the same for L^T q, (dL/dR)^T q, L^T dq
+//   comp_of, line_sums, zero_inactive   a row's active targets, then its fillers: (slot0, nl, col); the first-order sums of one
+//   reduce_cont_R        the continuum / R / ncomp cells of a tile's partials
+//   tap_m2, tap_centre   sum_k w_k (k - n)^2 and c_k = (k - n)^2 - that
+// Every sum keeps ONE order (no atomics), so a row's bits do not depend on its batch, its pass or its device: each
+// accumulator of a walk is its own sequential sum over k, acc += taps[k] * f, divided by bot after the loop; block_sum /
+// block_sum3 are a fixed LDS tree; finalize sums the tiles in order.  The convolutions read the workspace in HBM, so any LSF
+// width the likelihood accepts works.
 #include <hip/hip_runtime.h>
 
 #include "grad_args.h"
@@ -79,9 +78,163 @@ __device__ __forceinline__ void block_sum3(double& x, double& y, double& z, doub
     x = lds[0]; y = lds[kGradBlock]; z = lds[2 * kGradBlock];
 }
 
-// Component slots of the record list: the ncompmax * nlines target slots, then the nfill filler slots.
+// ---- the LSF walks ----
+
+// The sums a forward walk carries besides L F; the others stay 0 and cost nothing (kWhat is a template argument).
+enum : unsigned { kLsfR = 1, kLsfRR = 2, kLsfT = 4, kLsfRT = 8 };          // (dL/dR) F, (d2L/dR2) F, L T, (dL/dR) T
+struct Lsf { double cF, rF, rrF, cT, rT; };
+
+// The context's convolution at pixel i of row r, applied to F (a.F) and, with kLsfT, to T (a.q).
+template <unsigned kWhat>
+__device__ __forceinline__ Lsf lsf_forward(const GradArgs& a, const RowInfo& ri, int r, int i) {
+    const double* F = a.F + (size_t)r * a.npix;
+    const double* T = a.q + (size_t)r * a.npix;
+    const double* taps = a.taps + (size_t)r * a.tapcap;
+    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
+    const double* ddtaps = (kWhat & kLsfRR) ? a.ddtaps + (size_t)r * a.tapcap : nullptr;   // (no such workspace outside the HVP)
+    Lsf s = {0.0, 0.0, 0.0, 0.0, 0.0};
+    auto tap = [&](int k, int j) {                                             // tap k reads pixel j
+        const double f = F[j];
+        s.cF += taps[k] * f;
+        if (kWhat & kLsfR) s.rF += dtaps[k] * f;
+        if (kWhat & kLsfRR) s.rrF += ddtaps[k] * f;
+        if (kWhat & kLsfT) {
+            const double tt = T[j];
+            s.cT += taps[k] * tt;
+            if (kWhat & kLsfRT) s.rT += dtaps[k] * tt;
+        }
+    };
+    const int h = ri.n;
+    if (a.jax ? (i < h || i >= a.npix - h) : h == 0) {                         // :677-681 edge reset; R <= velstep: no convolution (:445)
+        s.cF = F[i];
+        if (kWhat & kLsfT) s.cT = T[i];
+    } else if (a.jax) {
+        for (int k = 0; k <= 2 * h; ++k) tap(k, i + k - h);
+    } else {
+        int j = (int)(((long)i - h) % a.npix);
+        if (j < 0) j += a.npix;
+        for (int k = 0; k <= 2 * h; ++k) {                                     // periodic boundary (:463-464)
+            tap(k, j);
+            if (++j == a.npix) j = 0;
+        }
+        s.cF = s.cF / ri.bot; s.rF = s.rF / ri.bot; s.rrF = s.rrF / ri.bot; s.cT = s.cT / ri.bot; s.rT = s.rT / ri.bot;
+    }
+    return s;
+}
+
+// The transpose at pixel i: L^T q and, with kTan, (dL/dR)^T q and L^T dq.
+struct LsfT { double lq, rq, ldq; };
+
+template <bool kTan>
+__device__ __forceinline__ LsfT lsf_transposed(const GradArgs& a, const RowInfo& ri, int r, int i, const double* q, const double* dq) {
+    const double* taps = a.taps + (size_t)r * a.tapcap;
+    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
+    LsfT s = {0.0, 0.0, 0.0};
+    auto tap = [&](int k, int o) {                                             // output o read pixel i through tap k
+        const double qo = q[o];
+        s.lq += taps[k] * qo;
+        if (kTan) {
+            s.rq += dtaps[k] * qo;
+            s.ldq += taps[k] * dq[o];
+        }
+    };
+    const int h = ri.n;
+    if (a.jax ? (i < h || i >= a.npix - h) : h == 0) {                         // an edge pixel is its own output; no taps
+        s.lq = q[i];
+        if (kTan) s.ldq = dq[i];
+    }
+    if (a.jax) {
+        // interior outputs o = i - k + h with tap k read pixel i
+        const int klo = max(0, i + 2 * h - a.npix + 1), khi = min(2 * h, i);
+        for (int k = klo; k <= khi; ++k) tap(k, i - k + h);
+    } else if (h > 0) {
+        int j = (int)(((long)i + h) % a.npix);
+        for (int k = 0; k <= 2 * h; ++k) {
+            tap(k, j);
+            if (--j < 0) j = a.npix - 1;
+        }
+        s.lq = s.lq / ri.bot; s.rq = s.rq / ri.bot; s.ldq = s.ldq / ri.bot;
+    }
+    return s;
+}
+
+// ---- the walk over a row's components ----
+
 __device__ __forceinline__ const double* rec_of(const GradArgs& a, int r, int slot) {
     return a.recs + ((size_t)r * a.nslots + slot) * kGradRec;
+}
+
+// Component c of a row's ri.nc + a.nfill: the active targets, then the fillers.  Its records are slots [slot0, slot0 + nl) of
+// the record list (the ncompmax * nlines target slots, then the nfill filler slots); its (N, z, b) are columns [col, col + 3).
+struct Comp { int slot0, nl, col; };
+
+__device__ __forceinline__ Comp comp_of(const GradArgs& a, const RowInfo& ri, int c) {
+    const bool fill = c >= ri.nc;
+    Comp o;
+    o.slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
+    o.nl = fill ? 1 : a.nlines;
+    o.col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
+    return o;
+}
+
+// First order, summed over a component's lines at one pixel: tau, dtau/dz, dtau/db (dtau/dN = ln10 tau).
+struct LineSums { double sN, sz, sb; };
+
+__device__ __forceinline__ LineSums line_sums(const GradArgs& a, int r, const Comp& k, double nu) {
+    LineSums s = {0.0, 0.0, 0.0};
+    for (int l = 0; l < k.nl; ++l) {
+        const double* rec = rec_of(a, r, k.slot0 + l);
+        const double u = nu * rec[0] - rec[1], y = rec[2], K = rec[3];
+        double wr, wi, dr, di, e;
+        faddeeva_dw(u, y, wr, wi, dr, di, e);
+        s.sN += K * wr;                                     // tau
+        s.sz += K * dr * (nu * rec[4]);                     // K H_u du/dz
+        s.sb -= K * rec[5] * e;                             // (K/b)(H + u H_u + a H_a)
+    }
+    return s;
+}
+
+// Inactive components: exactly 0 (one thread of the tile).
+__device__ __forceinline__ void zero_inactive(const GradArgs& a, const RowInfo& ri, double* out) {
+    for (int c = ri.nc; c < a.ncompmax; ++c) {
+        const int col = 1 + 3 * c + a.startind;
+        out[col] = out[col + 1] = out[col + 2] = 0.0;
+    }
+}
+
+__device__ __forceinline__ double* part_of(const GradArgs& a, int r) {
+    return a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
+}
+
+// A tile's continuum and R partials summed over its pixels, and the ncomp cell.  has_R false: the R cell is exactly 0.
+__device__ __forceinline__ void reduce_cont_R(const GradArgs& a, int r, double pc, double pR, bool has_R, double* lds) {
+    pc = block_sum(pc, lds);
+    pR = block_sum(pR, lds);
+    if (threadIdx.x == 0) {
+        double* out = part_of(a, r);
+        if (a.freespecres) out[0] = has_R ? pR : 0.0;
+        if (a.freecont) out[a.freespecres ? 1 : 0] = pc;
+        out[a.startind] = 0.0;                                                     // the ncomp slot
+    }
+}
+
+// ---- tap moments ----
+
+__device__ __forceinline__ bool no_taps(const GradArgs& a, int n) { return !a.jax && n == 0; }
+
+// sum_k w_k (k - n)^2 over the 2n + 1 taps (each thread reads the taps it wrote itself); every thread gets it.
+__device__ __forceinline__ double tap_m2(const double* taps, int n, double* lds) {
+    double m2 = 0.0;
+    for (int k = threadIdx.x; k <= 2 * n; k += kGradBlock) {
+        const double dk = (double)(k - n);
+        m2 += taps[k] * dk * dk;
+    }
+    return block_sum(m2, lds);
+}
+
+__device__ __forceinline__ double tap_centre(int k, int n, double m2) {
+    const double dk = (double)(k - n);
+    return dk * dk - m2;
 }
 
 }  // namespace
@@ -139,20 +292,16 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_setup_kernel(const Grad
         s += exp(-(dk * dk) * inv2s2);
     }
     const double wsum = block_sum(s, lds);
-    double m2 = 0.0;
     for (int k = t; k <= 2 * n; k += kGradBlock) {
         const double dk = (double)(k - n);
-        const double w = (!a.jax && n == 0) ? 1.0 : exp(-(dk * dk) * inv2s2) / wsum;
-        taps[k] = w;
-        m2 += w * dk * dk;
+        taps[k] = no_taps(a, n) ? 1.0 : exp(-(dk * dk) * inv2s2) / wsum;
     }
-    m2 = block_sum(m2, lds);
+    const double m2 = tap_m2(taps, n, lds);
     double bs = 0.0;
     const double dsig = 1.0 / (kFwhmToSigma * a.velstep * sigma * sigma * sigma);     // dsigma/dR / sigma^3
     for (int k = t; k <= 2 * n; k += kGradBlock) {
-        const double dk = (double)(k - n);
         const double w = taps[k];
-        dtaps[k] = (!a.jax && n == 0) ? 0.0 : w * (dk * dk - m2) * dsig;
+        dtaps[k] = no_taps(a, n) ? 0.0 : w * tap_centre(k, n, m2) * dsig;
         bs += w;
     }
     const double bot = block_sum(bs, lds);                                         // astropy divides by the tap sum (1 to rounding)
@@ -163,6 +312,8 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_setup_kernel(const Grad
     }
 }
 
+// tau is ONE accumulator over every slot in the walk's order; jvp_forward sums per component first.  The two associations
+// differ in their bits, so neither kernel takes the other's form.
 __global__ __launch_bounds__(kGradBlock) void mcalf_grad_forward_kernel(const GradArgs a) {
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
@@ -170,12 +321,14 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_forward_kernel(const Gr
     const RowInfo ri = row_info(a, r);
     const double nu = a.nu[i];
     double tau = 0.0;
-    const int nt = ri.nc * a.nlines;
-    for (int slot = 0; slot < nt + a.nfill; ++slot) {
-        const double* rec = rec_of(a, r, slot < nt ? slot : a.ncompmax * a.nlines + (slot - nt));
-        double wr, wi, dr, di, e;
-        faddeeva_dw(nu * rec[0] - rec[1], rec[2], wr, wi, dr, di, e);
-        tau += rec[3] * wr;
+    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+        const Comp k = comp_of(a, ri, c);
+        for (int l = 0; l < k.nl; ++l) {
+            const double* rec = rec_of(a, r, k.slot0 + l);
+            double wr, wi, dr, di, e;
+            faddeeva_dw(nu * rec[0] - rec[1], rec[2], wr, wi, dr, di, e);
+            tau += rec[3] * wr;
+        }
     }
     a.F[(size_t)r * a.npix + i] = exp(-tau);
 }
@@ -186,61 +339,23 @@ __device__ __forceinline__ void model_tile(const GradArgs& a, double* lds) {
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
     const RowInfo ri = row_info(a, r);
-    const double* F = a.F + (size_t)r * a.npix;
-    const double* taps = a.taps + (size_t)r * a.tapcap;
-    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
     double pc = 0.0, pR = 0.0;
     if (i < a.npix) {
-        double conv, dconv = 0.0;
-        if (a.jax) {
-            const int h = ri.n;
-            if (i < h || i >= a.npix - h) {
-                conv = F[i];                                                       // :677-681 edge reset
-            } else {
-                double c = 0.0, d = 0.0;
-                for (int k = 0; k <= 2 * h; ++k) {
-                    const double f = F[i + k - h];
-                    c += taps[k] * f;
-                    d += dtaps[k] * f;
-                }
-                conv = c; dconv = d;
-            }
-        } else if (ri.n > 0) {
-            const int n = ri.n;
-            int j = (int)(((long)i - n) % a.npix);
-            if (j < 0) j += a.npix;
-            double c = 0.0, d = 0.0;
-            for (int k = 0; k <= 2 * n; ++k) {                                     // periodic boundary (:463-464)
-                const double f = F[j];
-                c += taps[k] * f;
-                d += dtaps[k] * f;
-                if (++j == a.npix) j = 0;
-            }
-            conv = c / ri.bot; dconv = d / ri.bot;
-        } else {
-            conv = F[i];                                                           // R <= velstep: no convolution (:445)
-        }
+        const Lsf s = lsf_forward<kLsfR>(a, ri, r, i);
         double qv;
         if (kCot) {
             qv = a.q[(size_t)r * a.npix + i];
         } else {
             const double is2 = a.ispec2[i];
-            const double res = a.obj[i] - ri.cont * conv;
+            const double res = a.obj[i] - ri.cont * s.cF;
             const double term = is2 * res * res - a.lgis[i];
             qv = isnan(term) ? 0.0 : is2 * res;                                    // the pixels nansum keeps (:294)
             a.q[(size_t)r * a.npix + i] = qv;
         }
-        pc = qv * conv;
-        pR = qv * ri.cont * dconv;
+        pc = qv * s.cF;
+        pR = qv * ri.cont * s.rF;
     }
-    pc = block_sum(pc, lds);
-    pR = block_sum(pR, lds);
-    if (threadIdx.x == 0) {
-        double* out = a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
-        if (a.freespecres) out[0] = pR;
-        if (a.freecont) out[a.freespecres ? 1 : 0] = pc;
-        out[a.startind] = 0.0;                                                     // the ncomp slot
-    }
+    reduce_cont_R(a, r, pc, pR, true, lds);
 }
 
 __global__ __launch_bounds__(kGradBlock) void mcalf_grad_model_kernel(const GradArgs a) {
@@ -258,29 +373,9 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_adjoint_kernel(const Gr
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
     if (i >= a.npix) return;
     const RowInfo ri = row_info(a, r);
-    const double* q = a.q + (size_t)r * a.npix;
-    const double* taps = a.taps + (size_t)r * a.tapcap;
-    double rt;
-    if (a.jax) {
-        const int h = ri.n;
-        rt = (i < h || i >= a.npix - h) ? q[i] : 0.0;
-        // interior outputs o = i - k + h with tap k read pixel i
-        const int klo = max(0, i + 2 * h - a.npix + 1), khi = min(2 * h, i);
-        for (int k = klo; k <= khi; ++k) rt += taps[k] * q[i - k + h];
-    } else if (ri.n > 0) {
-        const int n = ri.n;
-        int j = (int)(((long)i + n) % a.npix);
-        double c = 0.0;
-        for (int k = 0; k <= 2 * n; ++k) {                                         // output j read pixel i through tap k
-            c += taps[k] * q[j];
-            if (--j < 0) j = a.npix - 1;
-        }
-        rt = c / ri.bot;
-    } else {
-        rt = q[i];
-    }
+    const LsfT s = lsf_transposed<false>(a, ri, r, i, a.q + (size_t)r * a.npix, nullptr);
     double* F = a.F + (size_t)r * a.npix;
-    F[i] = -F[i] * ri.cont * rt;
+    F[i] = -F[i] * ri.cont * s.lq;
 }
 
 __global__ __launch_bounds__(kGradBlock) void mcalf_grad_deriv_kernel(const GradArgs a) {
@@ -291,34 +386,15 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_deriv_kernel(const Grad
     const bool valid = i < a.npix;
     const double g = valid ? a.F[(size_t)r * a.npix + i] : 0.0;
     const double nu = valid ? a.nu[i] : a.nu[0];
-    double* out = a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
-    const int ncomp = ri.nc + a.nfill;                 // active targets, then the fillers
-    for (int c = 0; c < ncomp; ++c) {
-        const bool fill = c >= ri.nc;
-        const int slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
-        const int nl = fill ? 1 : a.nlines;
-        double sN = 0.0, sz = 0.0, sb = 0.0;
-        for (int l = 0; l < nl; ++l) {
-            const double* rec = rec_of(a, r, slot0 + l);
-            const double u = nu * rec[0] - rec[1], y = rec[2], K = rec[3];
-            double wr, wi, dr, di, e;
-            faddeeva_dw(u, y, wr, wi, dr, di, e);
-            sN += K * wr;                                   // tau
-            sz += K * dr * (nu * rec[4]);                   // K H_u du/dz
-            sb -= K * rec[5] * e;                           // (K/b)(H + u H_u + a H_a)
-        }
-        sN *= g * kLn10; sz *= g; sb *= g;
-        block_sum3(sN, sz, sb, lds);
-        if (threadIdx.x == 0) {
-            const int col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
-            out[col] = sN; out[col + 1] = sz; out[col + 2] = sb;
-        }
+    double* out = part_of(a, r);
+    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+        const Comp k = comp_of(a, ri, c);
+        LineSums s = line_sums(a, r, k, nu);
+        s.sN *= g * kLn10; s.sz *= g; s.sb *= g;
+        block_sum3(s.sN, s.sz, s.sb, lds);
+        if (threadIdx.x == 0) { out[k.col] = s.sN; out[k.col + 1] = s.sz; out[k.col + 2] = s.sb; }
     }
-    if (threadIdx.x == 0)
-        for (int c = ri.nc; c < a.ncompmax; ++c) {     // inactive components: exactly 0
-            const int col = 1 + 3 * c + a.startind;
-            out[col] = out[col + 1] = out[col + 2] = 0.0;
-        }
+    if (threadIdx.x == 0) zero_inactive(a, ri, out);
 }
 
 // kVeto: rows whose logL is -inf (veto) or NaN get NaN too (the VJP has no logL).
@@ -343,9 +419,9 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_finalize_kernel(const G
 
 __global__ __launch_bounds__(kGradBlock) void mcalf_vjp_finalize_kernel(const GradArgs a) { finalize_cell<false>(a); }
 
-// JVP, the one Voigt pass: per pixel tau and its directional derivative along the row's tangent.  The per-slot arithmetic
-// is mcalf_grad_deriv_kernel's, contracted with v instead of reduced over pixels.  Records and tangent entries are
-// row-uniform (scalar loads); the ncomp slot of v and the (N, z, b) of inactive components are never read.
+// JVP, the one Voigt pass: per pixel tau and its directional derivative along the row's tangent, the deriv kernel's line sums
+// contracted with v instead of reduced over pixels.  Records and tangent entries are row-uniform (scalar loads); the ncomp
+// slot of v and the (N, z, b) of inactive components are never read.
 __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_forward_kernel(const GradArgs a) {
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
@@ -354,31 +430,18 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_forward_kernel(const Gra
     const double* v = a.V + (size_t)r * a.ndim;
     const double nu = a.nu[i];
     double tau = 0.0, dtau = 0.0;
-    const int ncomp = ri.nc + a.nfill;                 // active targets, then the fillers
-    for (int c = 0; c < ncomp; ++c) {
-        const bool fill = c >= ri.nc;
-        const int slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
-        const int nl = fill ? 1 : a.nlines;
-        const int col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
-        double sN = 0.0, sz = 0.0, sb = 0.0;
-        for (int l = 0; l < nl; ++l) {
-            const double* rec = rec_of(a, r, slot0 + l);
-            const double u = nu * rec[0] - rec[1], y = rec[2], K = rec[3];
-            double wr, wi, dr, di, e;
-            faddeeva_dw(u, y, wr, wi, dr, di, e);
-            sN += K * wr;                                   // tau
-            sz += K * dr * (nu * rec[4]);                   // K H_u du/dz
-            sb -= K * rec[5] * e;                           // (K/b)(H + u H_u + a H_a)
-        }
-        tau += sN;
-        dtau += kLn10 * sN * v[col] + sz * v[col + 1] + sb * v[col + 2];
+    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+        const Comp k = comp_of(a, ri, c);
+        const LineSums s = line_sums(a, r, k, nu);
+        tau += s.sN;
+        dtau += kLn10 * s.sN * v[k.col] + s.sz * v[k.col + 1] + s.sb * v[k.col + 2];
     }
     const double F = exp(-tau);
     a.F[(size_t)r * a.npix + i] = F;
     a.q[(size_t)r * a.npix + i] = -F * dtau;
 }
 
-// JVP, the convolutions: dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F), the three modes of model_tile.
+// JVP, the convolutions: dM = cont L(T) + v_cont L(F) + v_R cont (dL/dR)(F).
 __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_model_kernel(const GradArgs a) {
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
@@ -389,45 +452,11 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_model_kernel(const GradA
         out[i] = NAN;
         return;
     }
-    const double* F = a.F + (size_t)r * a.npix;
-    const double* T = a.q + (size_t)r * a.npix;
-    const double* taps = a.taps + (size_t)r * a.tapcap;
-    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
     const double* v = a.V + (size_t)r * a.ndim;
     const double vR = a.freespecres ? v[0] : 0.0;
     const double vc = a.freecont ? v[a.freespecres ? 1 : 0] : 0.0;
-    double cF, cT, dF = 0.0;
-    if (a.jax) {
-        const int h = ri.n;
-        if (i < h || i >= a.npix - h) {
-            cF = F[i]; cT = T[i];                                                  // edge reset
-        } else {
-            double c = 0.0, d = 0.0, ct = 0.0;
-            for (int k = 0; k <= 2 * h; ++k) {
-                const double f = F[i + k - h];
-                c += taps[k] * f;
-                d += dtaps[k] * f;
-                ct += taps[k] * T[i + k - h];
-            }
-            cF = c; dF = d; cT = ct;
-        }
-    } else if (ri.n > 0) {
-        const int n = ri.n;
-        int j = (int)(((long)i - n) % a.npix);
-        if (j < 0) j += a.npix;
-        double c = 0.0, d = 0.0, ct = 0.0;
-        for (int k = 0; k <= 2 * n; ++k) {                                         // periodic boundary
-            const double f = F[j];
-            c += taps[k] * f;
-            d += dtaps[k] * f;
-            ct += taps[k] * T[j];
-            if (++j == a.npix) j = 0;
-        }
-        cF = c / ri.bot; dF = d / ri.bot; cT = ct / ri.bot;
-    } else {
-        cF = F[i]; cT = T[i];                                                      // R <= velstep: no convolution
-    }
-    out[i] = ri.cont * cT + vc * cF + vR * ri.cont * dF;
+    const Lsf s = lsf_forward<kLsfR | kLsfT>(a, ri, r, i);
+    out[i] = ri.cont * s.cT + vc * s.cF + vR * ri.cont * s.rF;
 }
 
 // ---- The Hessian-vector product of logL (mcalf_loglike_hvp_batch): forward mode over the gradient's reverse pass. ----
@@ -439,7 +468,6 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_model_kernel(const GradA
 //     (H v)_k    = sum_i [dg_i dtau_i/dtheta_k + g_i sum_k' d2tau_i/dtheta_k dtheta_k' v_k']      k, k' the (N, z, b) of ONE component
 // Per (component, line), s = nu/dnu (du/dz), z = u + i a ~ 1/b:
 //     d2tau/dN dtheta = ln10 dtau/dtheta,   d2tau/dz2 = K s^2 Re w'',   d2tau/dz db = -(K s/b) Re (z w)'',   d2tau/db2 = (K/b^2) Re (z^2 w)''
-// A pass: setup, hvp_taps, jvp_forward, hvp_model, hvp_adjoint, hvp_deriv, grad_finalize (the gradient's own, veto rule included).
 // The entries of v that are 0 columns of the gradient are never read; R's is not read either when the row has no taps (R <= velstep).
 
 namespace {
@@ -467,144 +495,59 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_taps_kernel(const GradAr
     const double* taps = a.taps + (size_t)r * a.tapcap;
     double* ddtaps = a.ddtaps + (size_t)r * a.tapcap;
     const double sigma = (ri.R / kFwhmToSigma) / a.velstep;
-    double m2 = 0.0;
-    for (int k = t; k <= 2 * n; k += kGradBlock) {
-        const double dk = (double)(k - n);
-        m2 += taps[k] * dk * dk;
-    }
-    m2 = block_sum(m2, lds);
+    const double m2 = tap_m2(taps, n, lds);
     double var = 0.0;
     for (int k = t; k <= 2 * n; k += kGradBlock) {
-        const double dk = (double)(k - n);
-        const double c = dk * dk - m2;
+        const double c = tap_centre(k, n, m2);
         var += taps[k] * c * c;
     }
     var = block_sum(var, lds);
     const double s2 = sigma * sigma, is4 = 1.0 / (s2 * s2), is6 = is4 / s2;
     const double dsdR = 1.0 / (kFwhmToSigma * a.velstep);
     for (int k = t; k <= 2 * n; k += kGradBlock) {
-        const double dk = (double)(k - n);
-        const double c = dk * dk - m2;
-        ddtaps[k] = (!a.jax && n == 0) ? 0.0 : taps[k] * ((c * c - var) * is6 - 3.0 * c * is4) * (dsdR * dsdR);
+        const double c = tap_centre(k, n, m2);
+        ddtaps[k] = no_taps(a, n) ? 0.0 : taps[k] * ((c * c - var) * is6 - 3.0 * c * is4) * (dsdR * dsdR);
     }
 }
 
-// q, dq and the continuum / R partials of H v: ONE tap loop gives L(F), (dL/dR) F, (d2L/dR2) F, L(T), (dL/dR) T.
+// q, dq and the continuum / R partials of H v from one forward walk with all five sums.
 __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_model_kernel(const GradArgs a) {
     __shared__ double lds[kGradBlock];
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
     const RowInfo ri = row_info(a, r);
     const RowTangent rt = row_tangent(a, r, ri);
-    const double* F = a.F + (size_t)r * a.npix;
-    const double* T = a.q + (size_t)r * a.npix;
-    const double* taps = a.taps + (size_t)r * a.tapcap;
-    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
-    const double* ddtaps = a.ddtaps + (size_t)r * a.tapcap;
     double pc = 0.0, pR = 0.0;
     if (i < a.npix) {
-        double cF, cT, rF = 0.0, rT = 0.0, rrF = 0.0;
-        if (a.jax) {
-            const int h = ri.n;
-            if (i < h || i >= a.npix - h) {
-                cF = F[i]; cT = T[i];                                              // edge reset
-            } else {
-                double c = 0.0, d = 0.0, dd = 0.0, ct = 0.0, dt = 0.0;
-                for (int k = 0; k <= 2 * h; ++k) {
-                    const double f = F[i + k - h], tt = T[i + k - h];
-                    c += taps[k] * f;
-                    d += dtaps[k] * f;
-                    dd += ddtaps[k] * f;
-                    ct += taps[k] * tt;
-                    dt += dtaps[k] * tt;
-                }
-                cF = c; rF = d; rrF = dd; cT = ct; rT = dt;
-            }
-        } else if (ri.n > 0) {
-            const int n = ri.n;
-            int j = (int)(((long)i - n) % a.npix);
-            if (j < 0) j += a.npix;
-            double c = 0.0, d = 0.0, dd = 0.0, ct = 0.0, dt = 0.0;
-            for (int k = 0; k <= 2 * n; ++k) {                                     // periodic boundary
-                const double f = F[j], tt = T[j];
-                c += taps[k] * f;
-                d += dtaps[k] * f;
-                dd += ddtaps[k] * f;
-                ct += taps[k] * tt;
-                dt += dtaps[k] * tt;
-                if (++j == a.npix) j = 0;
-            }
-            cF = c / ri.bot; rF = d / ri.bot; rrF = dd / ri.bot; cT = ct / ri.bot; rT = dt / ri.bot;
-        } else {
-            cF = F[i]; cT = T[i];                                                  // R <= velstep: no convolution
-        }
+        const Lsf s = lsf_forward<kLsfR | kLsfRR | kLsfT | kLsfRT>(a, ri, r, i);
         const double is2 = a.ispec2[i];
-        const double res = a.obj[i] - ri.cont * cF;
+        const double res = a.obj[i] - ri.cont * s.cF;
         const double term = is2 * res * res - a.lgis[i];
         const bool drop = isnan(term);                                             // the pixels nansum drops: W = 0
-        const double dM = ri.cont * cT + rt.vc * cF + rt.vR * ri.cont * rF;
+        const double dM = ri.cont * s.cT + rt.vc * s.cF + rt.vR * ri.cont * s.rF;
         const double qv = drop ? 0.0 : is2 * res;
         const double dqv = drop ? 0.0 : -is2 * dM;
         a.hq[(size_t)r * a.npix + i] = qv;
         a.hdq[(size_t)r * a.npix + i] = dqv;
-        pc = dqv * cF + qv * (cT + rt.vR * rF);
-        pR = (dqv * ri.cont + qv * rt.vc) * rF + qv * ri.cont * (rT + rt.vR * rrF);
+        pc = dqv * s.cF + qv * (s.cT + rt.vR * s.rF);
+        pR = (dqv * ri.cont + qv * rt.vc) * s.rF + qv * ri.cont * (s.rT + rt.vR * s.rrF);
     }
-    pc = block_sum(pc, lds);
-    pR = block_sum(pR, lds);
-    if (threadIdx.x == 0) {
-        double* out = a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
-        if (a.freespecres) out[0] = (a.jax || ri.n > 0) ? pR : 0.0;
-        if (a.freecont) out[a.freespecres ? 1 : 0] = pc;
-        out[a.startind] = 0.0;                                                     // the ncomp slot
-    }
+    reduce_cont_R(a, r, pc, pR, a.jax || ri.n > 0, lds);
 }
 
-// g and dg in place of F and T: ONE tap loop gives L^T q, (dL/dR)^T q, L^T dq.
+// g and dg in place of F and T from one transposed walk with all three sums.
 __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_adjoint_kernel(const GradArgs a) {
     const int r = blockIdx.y;
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
     if (i >= a.npix) return;
     const RowInfo ri = row_info(a, r);
     const RowTangent rt = row_tangent(a, r, ri);
-    const double* q = a.hq + (size_t)r * a.npix;
-    const double* dq = a.hdq + (size_t)r * a.npix;
-    const double* taps = a.taps + (size_t)r * a.tapcap;
-    const double* dtaps = a.dtaps + (size_t)r * a.tapcap;
-    double lq, rq = 0.0, ldq;
-    if (a.jax) {
-        const int h = ri.n;
-        const bool edge = i < h || i >= a.npix - h;
-        lq = edge ? q[i] : 0.0;
-        ldq = edge ? dq[i] : 0.0;
-        // interior outputs o = i - k + h with tap k read pixel i
-        const int klo = max(0, i + 2 * h - a.npix + 1), khi = min(2 * h, i);
-        for (int k = klo; k <= khi; ++k) {
-            const double qo = q[i - k + h];
-            lq += taps[k] * qo;
-            rq += dtaps[k] * qo;
-            ldq += taps[k] * dq[i - k + h];
-        }
-    } else if (ri.n > 0) {
-        const int n = ri.n;
-        int j = (int)(((long)i + n) % a.npix);
-        double c = 0.0, d = 0.0, cd = 0.0;
-        for (int k = 0; k <= 2 * n; ++k) {                                         // output j read pixel i through tap k
-            const double qo = q[j];
-            c += taps[k] * qo;
-            d += dtaps[k] * qo;
-            cd += taps[k] * dq[j];
-            if (--j < 0) j = a.npix - 1;
-        }
-        lq = c / ri.bot; rq = d / ri.bot; ldq = cd / ri.bot;
-    } else {
-        lq = q[i]; ldq = dq[i];
-    }
+    const LsfT s = lsf_transposed<true>(a, ri, r, i, a.hq + (size_t)r * a.npix, a.hdq + (size_t)r * a.npix);
     double* F = a.F + (size_t)r * a.npix;
     double* T = a.q + (size_t)r * a.npix;
     const double f = F[i], tt = T[i];
-    F[i] = -f * ri.cont * lq;
-    T[i] = -(tt * ri.cont + f * rt.vc) * lq - f * ri.cont * (rt.vR * rq + ldq);
+    F[i] = -f * ri.cont * s.lq;
+    T[i] = -(tt * ri.cont + f * rt.vc) * s.lq - f * ri.cont * (rt.vR * s.rq + s.ldq);
 }
 
 // The second-order Voigt pass: per active component the three sums of dg dtau/dtheta_k + g (d2tau/dtheta_k dtheta_k') v_k'.
@@ -618,16 +561,12 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_deriv_kernel(const GradA
     const double dg = valid ? a.q[(size_t)r * a.npix + i] : 0.0;
     const double nu = valid ? a.nu[i] : a.nu[0];
     const double* v = a.V + (size_t)r * a.ndim;
-    double* out = a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
-    const int ncomp = ri.nc + a.nfill;                 // active targets, then the fillers
-    for (int c = 0; c < ncomp; ++c) {
-        const bool fill = c >= ri.nc;
-        const int slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
-        const int nl = fill ? 1 : a.nlines;
-        const int col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
+    double* out = part_of(a, r);
+    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+        const Comp k = comp_of(a, ri, c);
         double tN = 0.0, tz = 0.0, tb = 0.0, tzz = 0.0, tzb = 0.0, tbb = 0.0;
-        for (int l = 0; l < nl; ++l) {
-            const double* rec = rec_of(a, r, slot0 + l);
+        for (int l = 0; l < k.nl; ++l) {
+            const double* rec = rec_of(a, r, k.slot0 + l);
             const double u = nu * rec[0] - rec[1], y = rec[2], K = rec[3], s = nu * rec[4], ib = rec[5];
             double wr, dr, e, d2, e2, e3;
             faddeeva_d2w(u, y, wr, dr, e, d2, e2, e3);
@@ -638,18 +577,14 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_deriv_kernel(const GradA
             tzb -= K * s * ib * e2;
             tbb += K * ib * ib * e3;
         }
-        const double vN = kLn10 * v[col], vz = v[col + 1], vb = v[col + 2];
+        const double vN = kLn10 * v[k.col], vz = v[k.col + 1], vb = v[k.col + 2];
         double sN = kLn10 * (dg * tN + g * (tN * vN + tz * vz + tb * vb));
         double sz = dg * tz + g * (tz * vN + tzz * vz + tzb * vb);
         double sb = dg * tb + g * (tb * vN + tzb * vz + tbb * vb);
         block_sum3(sN, sz, sb, lds);
-        if (threadIdx.x == 0) { out[col] = sN; out[col + 1] = sz; out[col + 2] = sb; }
+        if (threadIdx.x == 0) { out[k.col] = sN; out[k.col + 1] = sz; out[k.col + 2] = sb; }
     }
-    if (threadIdx.x == 0)
-        for (int c = ri.nc; c < a.ncompmax; ++c) {     // inactive components: exactly 0
-            const int col = 1 + 3 * c + a.startind;
-            out[col] = out[col + 1] = out[col + 2] = 0.0;
-        }
+    if (threadIdx.x == 0) zero_inactive(a, ri, out);
 }
 
 __global__ void mcalf_grad_hjert_kernel(const double* x, const double* y, long n, double* out) {
@@ -663,19 +598,15 @@ __global__ void mcalf_grad_hjert_kernel(const double* x, const double* y, long n
 }
 
 namespace mcalf {
-const void* grad_setup_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_setup_kernel); }
-const void* grad_forward_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_forward_kernel); }
-const void* grad_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_model_kernel); }
-const void* grad_adjoint_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_adjoint_kernel); }
-const void* grad_deriv_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_deriv_kernel); }
-const void* grad_finalize_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_finalize_kernel); }
-const void* vjp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_vjp_model_kernel); }
-const void* vjp_finalize_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_vjp_finalize_kernel); }
-const void* jvp_forward_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_jvp_forward_kernel); }
-const void* jvp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_jvp_model_kernel); }
-const void* hvp_taps_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_taps_kernel); }
-const void* hvp_model_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_model_kernel); }
-const void* hvp_adjoint_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_adjoint_kernel); }
-const void* hvp_deriv_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_hvp_deriv_kernel); }
-const void* grad_hjert_kernel_ptr() { return reinterpret_cast<const void*>(&mcalf_grad_hjert_kernel); }
+const void* grad_kernel_ptr(GradKernel k) {
+    static const void* const table[] = {                                           // in the order of enum GradKernel
+        (const void*)&mcalf_grad_setup_kernel,    (const void*)&mcalf_hvp_taps_kernel,
+        (const void*)&mcalf_grad_forward_kernel,  (const void*)&mcalf_grad_model_kernel,   (const void*)&mcalf_vjp_model_kernel,
+        (const void*)&mcalf_grad_adjoint_kernel,  (const void*)&mcalf_grad_deriv_kernel,   (const void*)&mcalf_jvp_forward_kernel,
+        (const void*)&mcalf_jvp_model_kernel,     (const void*)&mcalf_hvp_model_kernel,    (const void*)&mcalf_hvp_adjoint_kernel,
+        (const void*)&mcalf_hvp_deriv_kernel,     (const void*)&mcalf_grad_finalize_kernel, (const void*)&mcalf_vjp_finalize_kernel,
+        (const void*)&mcalf_grad_hjert_kernel};
+    static_assert(sizeof(table) / sizeof(table[0]) == kGradKernelCount, "one entry per GradKernel");
+    return table[k];
+}
 }  // namespace mcalf

@@ -262,15 +262,12 @@ struct mcalf_ctx {
     SampleHdr* d_whdr = nullptr;
     size_t cap_wide = 0, cap_wtaps = 0, cap_wpartial = 0, cap_wrows = 0, cap_whdr = 0;
     mcalf_launch_info_t last = {};      // what the last call did (mcalf_last_launch)
-    // Gradient and Jacobian-product entries (host_grad.cpp): per-row workspaces of one pass, F / q of its rows, per-tile
-    // partials, and the parameter / logL / gradient (or tangent) / pixel rows of the host-pointer entries (all grown on demand)
-    double *g_rows = nullptr, *g_recs = nullptr, *g_taps = nullptr, *g_dtaps = nullptr, *g_F = nullptr, *g_q = nullptr, *g_part = nullptr;
-    double *g_P = nullptr, *g_logL = nullptr, *g_G = nullptr, *g_X = nullptr;
-    size_t cap_g_rows = 0, cap_g_recs = 0, cap_g_taps = 0, cap_g_dtaps = 0, cap_g_F = 0, cap_g_q = 0, cap_g_part = 0;
-    size_t cap_g_P = 0, cap_g_logL = 0, cap_g_G = 0, cap_g_X = 0;
-    // The Hessian-vector product's own: the taps' second R derivative, q and dq of a pass, the tangent rows of the host entry
-    double *g_ddtaps = nullptr, *g_hq = nullptr, *g_hdq = nullptr, *g_V = nullptr;
-    size_t cap_g_ddtaps = 0, cap_g_hq = 0, cap_g_hdq = 0, cap_g_V = 0;
+    // The derivative entries' device buffers (host_grad.cpp), all grown on demand: the per-row workspaces of one pass -- the
+    // seven every product shares, then the HVP's three -- and the rows of a batch: logL, and the host-pointer entries' staging
+    // (parameters, tangents, gradients or H v, pixel rows).
+    enum { kGbRows, kGbRecs, kGbTaps, kGbDtaps, kGbF, kGbQ, kGbPart, kGbShared, kGbDdtaps = kGbShared, kGbHq, kGbHdq, kGbHvp,
+           kGbLogL = kGbHvp, kGbP, kGbV, kGbG, kGbX, kGbCount };
+    struct GradBuf { double* p = nullptr; size_t cap = 0; } gb[kGbCount];
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -366,8 +363,8 @@ void resident_stop(mcalf_ctx* ctx);
 bool resident_serves(const mcalf_ctx* ctx, int mode, int64_t batch, int rowlen, bool from_cube);
 int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out);
 
-// ---- host_grad.cpp: the analytic gradient of logL ------------------------------------------------------------------------
-void grad_release(mcalf_ctx* ctx);                     // frees the gradient workspaces
+// ---- host_grad.cpp: the derivative entries ----------------------------------------------------------------------------
+void grad_release(mcalf_ctx* ctx);                     // frees every buffer of ctx->gb
 
 // ---- comm.cpp -----------------------------------------------------------------------------------------------------------
 void comm_release(mcalf_ctx* ctx);

@@ -1,9 +1,9 @@
-// Host side of the analytic gradient of logL (grad_kernels.hip): mcalf_loglike_grad_batch[_device] and
-// mcalf_voigt_hjerting_grad.  logL itself comes from the likelihood's own launch (host_abi.cpp: launch), so the two
-// entries agree on it bit for bit; the gradient kernels then run over row blocks whose per-row workspaces stay within
-// kGradChunkBytes.  The model Jacobian's products with a vector, mcalf_model_jvp_batch[_device] and
-// mcalf_model_vjp_batch[_device], run over the same row blocks and workspaces.  The Hessian-vector product of logL,
-// mcalf_loglike_hvp_batch[_device], shares them too and adds three per-row workspaces, so its passes are cut smaller.
+// Host side of the derivative kernels (grad_kernels.hip): the analytic gradient of logL, the model Jacobian's JVP and VJP,
+// the Hessian-vector product of logL, and mcalf_voigt_hjerting_grad.  A product is a row of the table below -- its
+// workspaces, whether logL comes first, its kernel sequence, its row pointers -- and ONE driver (run_product) runs any of
+// them pass by pass over row blocks whose per-row workspaces stay within kGradChunkBytes.  logL itself comes from the
+// likelihood's own launch (host_abi.cpp: launch), so the entries agree on it bit for bit.  ONE helper serves the
+// host-pointer entries (run_host: staging, multi-device split) and one the device-pointer entries (run_device).
 #include <cmath>
 
 #include "grad_args.h"
@@ -18,52 +18,38 @@ int grad_ncap(const mcalf_ctx* ctx) {
 }
 int grad_tapcap(const mcalf_ctx* ctx) { return 2 * grad_ncap(ctx) + 1; }
 
-// Rows per pass: EVERY per-row workspace of a pass (F, q, taps and their R derivative, records, partials) within
-// kGradChunkBytes -- the taps of a wide-LSF context are thousands of doubles per row -- and at most kGradMaxRows rows:
-// the pixel kernels carry the row on grid.y (a short spectrum's rows are ~2 KB each, so the byte bound alone would
-// allow ~200 000 of them), the same cap as the likelihood's wide path (host_abi.cpp: wide_rows_per_pass).
+// Doubles per row of per-row workspace `b` (one of ctx->gb[0, kGbHvp)).
+int64_t ws_row_elems(const mcalf_ctx* ctx, int b) {
+    switch (b) {
+        case mcalf_ctx::kGbRows: return kGradRow;
+        case mcalf_ctx::kGbRecs: return (int64_t)grad_nslots(ctx) * kGradRec;
+        case mcalf_ctx::kGbPart: return (int64_t)grad_ntiles(ctx) * ctx->ndim;
+        case mcalf_ctx::kGbTaps: case mcalf_ctx::kGbDtaps: case mcalf_ctx::kGbDdtaps: return grad_tapcap(ctx);
+        default: return ctx->npix;                                                  // F, q, hq, hdq
+    }
+}
+
+// Rows per pass of a product whose per-row workspaces are ctx->gb[0, nws): EVERY one of them within kGradChunkBytes -- the
+// taps of a wide-LSF context are thousands of doubles per row -- and at most kGradMaxRows rows: the pixel kernels carry the
+// row on grid.y (a short spectrum's rows are ~2 KB each, so the byte bound alone would allow ~200 000 of them), the same cap
+// as the likelihood's wide path (host_abi.cpp: wide_rows_per_pass).  The HVP's three more workspaces cut its passes smaller.
 constexpr int64_t kGradMaxRows = 65535;
-// An HVP pass (`hvp`) also holds q, dq and the taps' second R derivative per row; the other entries' passes stay as they were.
-int64_t grad_chunk_rows(const mcalf_ctx* ctx, bool hvp = false) {
-    int64_t per_row = (2 * (int64_t)ctx->npix + 2 * (int64_t)grad_tapcap(ctx) + kGradRow +
-                       (int64_t)grad_nslots(ctx) * kGradRec + (int64_t)grad_ntiles(ctx) * ctx->ndim) * (int64_t)sizeof(double);
-    if (hvp) per_row += (2 * (int64_t)ctx->npix + (int64_t)grad_tapcap(ctx)) * (int64_t)sizeof(double);
+int64_t grad_chunk_rows(const mcalf_ctx* ctx, int nws) {
+    int64_t per_row = 0;
+    for (int b = 0; b < nws; ++b) per_row += ws_row_elems(ctx, b) * (int64_t)sizeof(double);
     return std::min<int64_t>(kGradMaxRows, std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row));
 }
 
-// Everything a pass of `rows` rows needs, grown once (a later call of as many rows or fewer allocates nothing).  The VJP
-// reads q from the caller's array and needs no q workspace (`own_q` false); its passes are cut as the gradient's all the same.
-int grad_prepare(mcalf_ctx* ctx, int64_t batch, bool own_q = true) {
-    const size_t rows = (size_t)std::min<int64_t>(batch, grad_chunk_rows(ctx));
-    int rc;
-    if ((rc = grow(ctx, &ctx->g_rows, &ctx->cap_g_rows, rows * kGradRow))) return rc;
-    if ((rc = grow(ctx, &ctx->g_recs, &ctx->cap_g_recs, rows * grad_nslots(ctx) * kGradRec))) return rc;
-    if ((rc = grow(ctx, &ctx->g_taps, &ctx->cap_g_taps, rows * grad_tapcap(ctx)))) return rc;
-    if ((rc = grow(ctx, &ctx->g_dtaps, &ctx->cap_g_dtaps, rows * grad_tapcap(ctx)))) return rc;
-    if ((rc = grow(ctx, &ctx->g_F, &ctx->cap_g_F, rows * ctx->npix))) return rc;
-    if (own_q && (rc = grow(ctx, &ctx->g_q, &ctx->cap_g_q, rows * ctx->npix))) return rc;
-    return grow(ctx, &ctx->g_part, &ctx->cap_g_part, rows * grad_ntiles(ctx) * ctx->ndim);
-}
-
-// The HVP's pass: the shared workspaces for its (smaller) row count, q, dq, the taps' second derivative, and logL of the batch.
-int hvp_prepare(mcalf_ctx* ctx, int64_t batch) {
-    const int64_t rows64 = std::min<int64_t>(batch, grad_chunk_rows(ctx, true));
-    const size_t rows = (size_t)rows64;
-    int rc;
-    if ((rc = grad_prepare(ctx, rows64))) return rc;
-    if ((rc = grow(ctx, &ctx->g_ddtaps, &ctx->cap_g_ddtaps, rows * grad_tapcap(ctx)))) return rc;
-    if ((rc = grow(ctx, &ctx->g_hq, &ctx->cap_g_hq, rows * ctx->npix))) return rc;
-    if ((rc = grow(ctx, &ctx->g_hdq, &ctx->cap_g_hdq, rows * ctx->npix))) return rc;
-    return grow(ctx, &ctx->g_logL, &ctx->cap_g_logL, (size_t)batch);
-}
+int grow_buf(mcalf_ctx* ctx, int b, size_t elems) { return grow(ctx, &ctx->gb[b].p, &ctx->gb[b].cap, elems); }
 
 // What every pass of a batch shares; the row pointers and the row count are set per pass.
 GradArgs grad_args(const mcalf_ctx* ctx) {
     GradArgs a = {};
+    const mcalf_ctx::GradBuf* gb = ctx->gb;
     a.nu = ctx->d_nu; a.obj = ctx->d_obj; a.ispec2 = ctx->d_ispec2; a.lgis = ctx->d_lgis; a.lines = ctx->d_lines;
-    a.rows = ctx->g_rows; a.recs = ctx->g_recs; a.taps = ctx->g_taps; a.dtaps = ctx->g_dtaps;
-    a.F = ctx->g_F; a.q = ctx->g_q; a.part = ctx->g_part;
-    a.ddtaps = ctx->g_ddtaps; a.hq = ctx->g_hq; a.hdq = ctx->g_hdq;
+    a.rows = gb[mcalf_ctx::kGbRows].p; a.recs = gb[mcalf_ctx::kGbRecs].p; a.taps = gb[mcalf_ctx::kGbTaps].p; a.dtaps = gb[mcalf_ctx::kGbDtaps].p;
+    a.F = gb[mcalf_ctx::kGbF].p; a.q = gb[mcalf_ctx::kGbQ].p; a.part = gb[mcalf_ctx::kGbPart].p;
+    a.ddtaps = gb[mcalf_ctx::kGbDdtaps].p; a.hq = gb[mcalf_ctx::kGbHq].p; a.hdq = gb[mcalf_ctx::kGbHdq].p;
     a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = grad_ntiles(ctx); a.tapcap = grad_tapcap(ctx); a.nslots = grad_nslots(ctx);
     a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax; a.nfill = ctx->nfill; a.startind = ctx->startind; a.endind = ctx->endind;
     a.freespecres = ctx->freespecres; a.freecont = ctx->freecont; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0;
@@ -72,253 +58,154 @@ GradArgs grad_args(const mcalf_ctx* ctx) {
     return a;
 }
 
-// One kernel of a pass: every kernel takes the argument block by value.
-int grad_kernel(mcalf_ctx* ctx, const void* fn, dim3 grid, const GradArgs& a, hipStream_t stream) {
-    void* args[] = {(void*)&a};
-    HIP_TRY(ctx, hipLaunchKernel(fn, grid, dim3(kGradBlock), args, 0, stream));
-    return MCALF_OK;
-}
+// The device rows of one call: parameters [batch, ndim], the second input (V or Q; none for the gradient), the primary
+// output (G, dM or HV) and logL [batch] (NULL: the context's own buffer).
+struct Call { const double *P, *X; double *Y, *L; };
 
-// setup, forward, model, adjoint, deriv, finalize over the rows of `a`; `vjp`: the cotangent variants of model and finalize.
-int grad_pass(mcalf_ctx* ctx, const GradArgs& a, bool vjp, hipStream_t stream) {
-    const dim3 px((unsigned)a.ntiles, (unsigned)a.nrows);
-    const int64_t cells = (int64_t)a.nrows * a.ndim;
-    int rc;
-    if ((rc = grad_kernel(ctx, grad_setup_kernel_ptr(), dim3((unsigned)a.nrows), a, stream))) return rc;
-    if ((rc = grad_kernel(ctx, grad_forward_kernel_ptr(), px, a, stream))) return rc;
-    if ((rc = grad_kernel(ctx, vjp ? vjp_model_kernel_ptr() : grad_model_kernel_ptr(), px, a, stream))) return rc;
-    if ((rc = grad_kernel(ctx, grad_adjoint_kernel_ptr(), px, a, stream))) return rc;
-    if ((rc = grad_kernel(ctx, grad_deriv_kernel_ptr(), px, a, stream))) return rc;
-    return grad_kernel(ctx, vjp ? vjp_finalize_kernel_ptr() : grad_finalize_kernel_ptr(),
-                       dim3((unsigned)((cells + kGradBlock - 1) / kGradBlock)), a, stream);
-}
+struct Product {
+    const char* device_entry;     // the name its device-pointer entry reports
+    int nws;                      // its per-row workspaces are ctx->gb[0, nws); they also cut its passes
+    bool own_q;                   // false: `q` is the caller's array, no q workspace is grown (the passes are cut all the same)
+    bool logl, l_out;             // logL of the batch first (the veto rule); logL is an output of the entry too
+    bool has_x, x_pix, y_pix;     // a second input; X / Y rows are npix wide (else ndim)
+    GradKernel seq[8];            // the kernels of a pass in order, kGradKernelCount after the last
+    void (*bind)(GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t row0);   // the row pointers of the pass at row0 (P is the driver's)
+};
 
-// logL of the batch (the likelihood's launch, which sizes its own workspaces -- per pass of rows on a wide-LSF context), then
-// the gradient kernels pass by pass; all on `stream`.
-int grad_launch(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG, hipStream_t stream) {
-    if (batch <= 0) return MCALF_OK;
-    int rc = grad_prepare(ctx, batch);
-    if (rc) return rc;
-    if ((rc = launch(ctx, kModeLogL, dP, batch, 0, 0, dlogL, nullptr, stream))) return rc;
-    GradArgs a = grad_args(ctx);
-    const int64_t chunk = grad_chunk_rows(ctx);
-    for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
-        a.P = dP + (size_t)row0 * ctx->ndim;
-        a.logL = dlogL + row0;
-        a.G = dG + (size_t)row0 * ctx->ndim;
-        a.nrows = (int)std::min(chunk, batch - row0);
-        if ((rc = grad_pass(ctx, a, false, stream))) return rc;
-    }
-    return MCALF_OK;
-}
-
+const Product kProdGrad = {"mcalf_loglike_grad_batch_device", mcalf_ctx::kGbShared, true, true, true, false, false, false,
+    {kGradSetup, kGradForward, kGradModel, kGradAdjoint, kGradDeriv, kGradFinalize, kGradKernelCount},
+    [](GradArgs& a, const Call& c, size_t cell0, size_t, int64_t row0) { a.logL = c.L + row0; a.G = c.Y + cell0; }};
 // dM = J(P) V row by row: setup, the tangent Voigt pass, the convolutions.
-int jvp_launch(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* ddM, hipStream_t stream) {
+const Product kProdJvp = {"mcalf_model_jvp_batch_device", mcalf_ctx::kGbShared, true, false, false, true, false, true,
+    {kGradSetup, kGradJvpForward, kGradJvpModel, kGradKernelCount},
+    [](GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t) { a.V = c.X + cell0; a.dM = c.Y + pix0; }};
+// G = J(P)^T Q row by row: the gradient's pass with the caller's cotangent rows as q (read only) and no logL.
+const Product kProdVjp = {"mcalf_model_vjp_batch_device", mcalf_ctx::kGbShared, false, false, false, true, true, false,
+    {kGradSetup, kGradForward, kGradVjpModel, kGradAdjoint, kGradDeriv, kGradVjpFinalize, kGradKernelCount},
+    [](GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t) { a.q = const_cast<double*>(c.X) + pix0; a.G = c.Y + cell0; }};
+// HV = (d2 logL / dtheta2)(P) V row by row: the taps' second derivative, the tangent Voigt pass, q / dq, g / dg, the
+// second-order Voigt pass and the gradient's finalize (logL, for its veto rule, stays in the context's buffer).
+const Product kProdHvp = {"mcalf_loglike_hvp_batch_device", mcalf_ctx::kGbHvp, true, true, false, true, false, false,
+    {kGradSetup, kGradHvpTaps, kGradJvpForward, kGradHvpModel, kGradHvpAdjoint, kGradHvpDeriv, kGradFinalize, kGradKernelCount},
+    [](GradArgs& a, const Call& c, size_t cell0, size_t, int64_t row0) { a.V = c.X + cell0; a.logL = c.L + row0; a.G = c.Y + cell0; }};
+
+dim3 grad_grid(GradKernel k, const GradArgs& a) {
+    if (k < kGradFirstPixel) return dim3((unsigned)a.nrows);
+    if (k < kGradFirstCell) return dim3((unsigned)a.ntiles, (unsigned)a.nrows);
+    return dim3((unsigned)(((int64_t)a.nrows * a.ndim + kGradBlock - 1) / kGradBlock));
+}
+
+// Product `p` over a batch, all on `stream`: its workspaces for one pass (grown once: a later call of as many rows or fewer
+// allocates nothing), logL of the batch where it needs one (the likelihood's launch, which sizes its own workspaces), then
+// its kernels pass by pass; every kernel takes the argument block by value.
+int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStream_t stream) {
     if (batch <= 0) return MCALF_OK;
-    int rc = grad_prepare(ctx, batch);
-    if (rc) return rc;
+    const int64_t chunk = grad_chunk_rows(ctx, p.nws);
+    const size_t rows = (size_t)std::min(batch, chunk);
+    int rc;
+    for (int b = 0; b < p.nws; ++b)
+        if ((b != mcalf_ctx::kGbQ || p.own_q) && (rc = grow_buf(ctx, b, rows * (size_t)ws_row_elems(ctx, b)))) return rc;
+    if (p.logl) {
+        if (!c.L) {
+            if ((rc = grow_buf(ctx, mcalf_ctx::kGbLogL, (size_t)batch))) return rc;
+            c.L = ctx->gb[mcalf_ctx::kGbLogL].p;
+        }
+        if ((rc = launch(ctx, kModeLogL, c.P, batch, 0, 0, c.L, nullptr, stream))) return rc;
+    }
     GradArgs a = grad_args(ctx);
-    const int64_t chunk = grad_chunk_rows(ctx);
     for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
-        a.P = dP + (size_t)row0 * ctx->ndim;
-        a.V = dV + (size_t)row0 * ctx->ndim;
-        a.dM = ddM + (size_t)row0 * ctx->npix;
+        a.P = c.P + (size_t)row0 * ctx->ndim;
         a.nrows = (int)std::min(chunk, batch - row0);
-        const dim3 px((unsigned)a.ntiles, (unsigned)a.nrows);
-        if ((rc = grad_kernel(ctx, grad_setup_kernel_ptr(), dim3((unsigned)a.nrows), a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, jvp_forward_kernel_ptr(), px, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, jvp_model_kernel_ptr(), px, a, stream))) return rc;
+        p.bind(a, c, (size_t)row0 * ctx->ndim, (size_t)row0 * ctx->npix, row0);
+        for (const GradKernel* k = p.seq; *k != kGradKernelCount; ++k) {
+            void* args[] = {(void*)&a};
+            HIP_TRY(ctx, hipLaunchKernel(grad_kernel_ptr(*k), grad_grid(*k, a), dim3(kGradBlock), args, 0, stream));
+        }
     }
     return MCALF_OK;
 }
 
-// G = J(P)^T Q row by row: the gradient's pass with the caller's cotangent rows as q (read only).
-int vjp_launch(mcalf_ctx* ctx, const double* dP, const double* dQ, int64_t batch, double* dG, hipStream_t stream) {
-    if (batch <= 0) return MCALF_OK;
-    int rc = grad_prepare(ctx, batch, false);
-    if (rc) return rc;
-    GradArgs a = grad_args(ctx);
-    const int64_t chunk = grad_chunk_rows(ctx);
-    for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
-        a.P = dP + (size_t)row0 * ctx->ndim;
-        a.q = const_cast<double*>(dQ) + (size_t)row0 * ctx->npix;
-        a.G = dG + (size_t)row0 * ctx->ndim;
-        a.nrows = (int)std::min(chunk, batch - row0);
-        if ((rc = grad_pass(ctx, a, true, stream))) return rc;
-    }
-    return MCALF_OK;
+int run_device(mcalf_ctx* ctx, const Product& p, const Call& c, int64_t batch, void* stream) {
+    if (!ctx || batch < 0 || (batch > 0 && (!c.P || !c.Y || (p.has_x && !c.X) || (p.l_out && !c.L))))
+        return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
+    MCALF_SINGLE_ONLY(ctx, p.device_entry);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    return run_product(ctx, p, c, batch, (hipStream_t)stream);
 }
 
-// HV = (d2 logL / dtheta2)(P) V row by row.  logL of the batch (for the veto rule) comes from the likelihood's launch into the
-// context's own g_logL; then per pass setup, the taps' second derivative, the tangent Voigt pass, q / dq, g / dg, the
-// second-order Voigt pass and the gradient's finalize.
-int hvp_launch(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dHV, hipStream_t stream) {
-    if (batch <= 0) return MCALF_OK;
-    int rc = hvp_prepare(ctx, batch);
-    if (rc) return rc;
-    if ((rc = launch(ctx, kModeLogL, dP, batch, 0, 0, ctx->g_logL, nullptr, stream))) return rc;
-    GradArgs a = grad_args(ctx);
-    const int64_t chunk = grad_chunk_rows(ctx, true);
-    for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
-        a.P = dP + (size_t)row0 * ctx->ndim;
-        a.V = dV + (size_t)row0 * ctx->ndim;
-        a.logL = ctx->g_logL + row0;
-        a.G = dHV + (size_t)row0 * ctx->ndim;
-        a.nrows = (int)std::min(chunk, batch - row0);
-        const dim3 px((unsigned)a.ntiles, (unsigned)a.nrows), row((unsigned)a.nrows);
-        const int64_t cells = (int64_t)a.nrows * a.ndim;
-        if ((rc = grad_kernel(ctx, grad_setup_kernel_ptr(), row, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, hvp_taps_kernel_ptr(), row, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, jvp_forward_kernel_ptr(), px, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, hvp_model_kernel_ptr(), px, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, hvp_adjoint_kernel_ptr(), px, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, hvp_deriv_kernel_ptr(), px, a, stream))) return rc;
-        if ((rc = grad_kernel(ctx, grad_finalize_kernel_ptr(), dim3((unsigned)((cells + kGradBlock - 1) / kGradBlock)), a, stream)))
-            return rc;
-    }
-    return MCALF_OK;
-}
+// A host-pointer entry: P and X to the device, the product, Y (and logL where the caller wants it: L may be NULL) back, all on
+// the context's stream; a multi-device context cuts the rows over its devices.
+struct HostShard { const Product* p; const double *P, *X; double *Y, *L; int64_t ndim, xw, yw; };
 
-// The host-pointer JVP (X = V [batch, ndim], Y = dM [batch, npix]) or VJP (X = Q [batch, npix], Y = G [batch, ndim]):
-// P and X to the device, the kernels, Y back, all on the context's stream; a multi-device context cuts the rows over
-// its devices.  g_G holds the [batch, ndim] operand (V in, or G out), g_X the [batch, npix] one.
-struct DerivShard { bool jvp; const double *P, *X; double* Y; int64_t xw, yw; int ndim; };
-
-int deriv_host(mcalf_ctx* ctx, bool jvp, const double* P, const double* X, int64_t batch, double* Y) {
-    if (!ctx || batch < 0 || (batch > 0 && (!P || !X || !Y))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
+int run_host(mcalf_ctx* ctx, const Product& p, const double* P, const double* X, int64_t batch, double* Y, double* L) {
+    if (!ctx || batch < 0 || (batch > 0 && (!P || !Y || (p.has_x && !X)))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
     if (batch == 0) return MCALF_OK;
-    const int64_t xw = jvp ? ctx->ndim : ctx->npix, yw = jvp ? ctx->npix : ctx->ndim;
+    const int64_t xw = p.x_pix ? ctx->npix : ctx->ndim, yw = p.y_pix ? ctx->npix : ctx->ndim;
     if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
-        DerivShard c = {jvp, P, X, Y, xw, yw, ctx->ndim};
+        HostShard c = {&p, P, X, Y, L, ctx->ndim, xw, yw};
         return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const DerivShard* s = static_cast<const DerivShard*>(arg);
-            return deriv_host(static_cast<mcalf_ctx*>(sub), s->jvp, s->P + (size_t)lo * s->ndim, s->X + (size_t)lo * s->xw, hi - lo,
-                              s->Y + (size_t)lo * s->yw);
+            const HostShard* s = static_cast<const HostShard*>(arg);
+            return run_host(static_cast<mcalf_ctx*>(sub), *s->p, s->P + (size_t)lo * s->ndim, s->X ? s->X + (size_t)lo * s->xw : nullptr,
+                            hi - lo, s->Y + (size_t)lo * s->yw, s->L ? s->L + lo : nullptr);
         }, &c);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)batch * ctx->ndim, pixels = (size_t)batch * ctx->npix;
+    const int bX = p.x_pix ? mcalf_ctx::kGbX : mcalf_ctx::kGbV, bY = p.y_pix ? mcalf_ctx::kGbX : mcalf_ctx::kGbG;
+    const size_t nP = (size_t)batch * ctx->ndim, nX = p.has_x ? (size_t)batch * xw : 0, nY = (size_t)batch * yw;
     int rc;
-    if ((rc = grow(ctx, &ctx->g_P, &ctx->cap_g_P, cells))) return rc;
-    if ((rc = grow(ctx, &ctx->g_G, &ctx->cap_g_G, cells))) return rc;
-    if ((rc = grow(ctx, &ctx->g_X, &ctx->cap_g_X, pixels))) return rc;
-    double *dX = jvp ? ctx->g_G : ctx->g_X, *dY = jvp ? ctx->g_X : ctx->g_G;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_P, P, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(dX, X, (size_t)batch * xw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = jvp ? jvp_launch(ctx, ctx->g_P, dX, batch, dY, ctx->stream) : vjp_launch(ctx, ctx->g_P, dX, batch, dY, ctx->stream)))
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(Y, dY, (size_t)batch * yw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = grow_buf(ctx, mcalf_ctx::kGbP, nP)) || (rc = grow_buf(ctx, bX, nX)) || (rc = grow_buf(ctx, bY, nY))) return rc;
+    const mcalf_ctx::GradBuf* gb = ctx->gb;
+    HIP_TRY(ctx, hipMemcpyAsync(gb[mcalf_ctx::kGbP].p, P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (p.has_x) HIP_TRY(ctx, hipMemcpyAsync(gb[bX].p, X, nX * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_product(ctx, p, {gb[mcalf_ctx::kGbP].p, p.has_x ? gb[bX].p : nullptr, gb[bY].p, nullptr}, batch, ctx->stream))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(Y, gb[bY].p, nY * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (L) HIP_TRY(ctx, hipMemcpyAsync(L, gb[mcalf_ctx::kGbLogL].p, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->last.path = MCALF_PATH_HOST_STAGED;
+    ctx->last.path = MCALF_PATH_HOST_STAGED;              // H2D, launch, D2H on the context's stream (set after the launch's own)
     ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
     ctx->last.pinned_out = is_pinned_host(Y) ? 1 : 0;
     return MCALF_OK;
 }
 
-int deriv_device(mcalf_ctx* ctx, bool jvp, const double* dP, const double* dX, int64_t batch, double* dY, void* stream) {
-    if (!ctx || batch < 0 || (batch > 0 && (!dP || !dX || !dY))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
-    MCALF_SINGLE_ONLY(ctx, jvp ? "mcalf_model_jvp_batch_device" : "mcalf_model_vjp_batch_device");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
-    return jvp ? jvp_launch(ctx, dP, dX, batch, dY, (hipStream_t)stream) : vjp_launch(ctx, dP, dX, batch, dY, (hipStream_t)stream);
-}
-
 }  // namespace
 
 void grad_release(mcalf_ctx* ctx) {
-    double* bufs[] = {ctx->g_rows, ctx->g_recs, ctx->g_taps, ctx->g_dtaps, ctx->g_F, ctx->g_q, ctx->g_part, ctx->g_P, ctx->g_logL, ctx->g_G, ctx->g_X,
-                      ctx->g_ddtaps, ctx->g_hq, ctx->g_hdq, ctx->g_V};
-    for (double* b : bufs)
-        if (b) (void)hipFree(b);
+    for (mcalf_ctx::GradBuf& b : ctx->gb)
+        if (b.p) (void)hipFree(b.p);
 }
 
 extern "C" int mcalf_loglike_grad_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG,
                                                void* stream) {
-    if (!ctx || batch < 0 || (batch > 0 && (!dP || !dlogL || !dG))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
-    MCALF_SINGLE_ONLY(ctx, "mcalf_loglike_grad_batch_device");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
-    return grad_launch(ctx, dP, batch, dlogL, dG, (hipStream_t)stream);
+    return run_device(ctx, kProdGrad, {dP, nullptr, dG, dlogL}, batch, stream);
 }
 
 extern "C" int mcalf_loglike_grad_batch(mcalf_ctx* ctx, const double* P, int64_t batch, double* logL, double* G) {
-    if (!ctx || batch < 0 || (batch > 0 && (!P || !G))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
-    if (batch == 0) return MCALF_OK;
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
-        struct GradShard { const double* P; double *logL, *G; int ndim; } c = {P, logL, G, ctx->ndim};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const GradShard* s = static_cast<const GradShard*>(arg);
-            return mcalf_loglike_grad_batch(static_cast<mcalf_ctx*>(sub), s->P + (size_t)lo * s->ndim, hi - lo,
-                                            s->logL ? s->logL + lo : nullptr, s->G + (size_t)lo * s->ndim);
-        }, &c);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)batch * ctx->ndim;
-    int rc;
-    if ((rc = grow(ctx, &ctx->g_P, &ctx->cap_g_P, cells))) return rc;
-    if ((rc = grow(ctx, &ctx->g_G, &ctx->cap_g_G, cells))) return rc;
-    if ((rc = grow(ctx, &ctx->g_logL, &ctx->cap_g_logL, (size_t)batch))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_P, P, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = grad_launch(ctx, ctx->g_P, batch, ctx->g_logL, ctx->g_G, ctx->stream))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(G, ctx->g_G, cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (logL) HIP_TRY(ctx, hipMemcpyAsync(logL, ctx->g_logL, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->last.path = MCALF_PATH_HOST_STAGED;              // H2D, launch, D2H on the context's stream (set after the launch's own)
-    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
-    ctx->last.pinned_out = is_pinned_host(G) ? 1 : 0;
-    return MCALF_OK;
+    return run_host(ctx, kProdGrad, P, nullptr, batch, G, logL);
 }
 
 extern "C" int mcalf_model_jvp_batch(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* dM) {
-    return deriv_host(ctx, true, P, V, batch, dM);
+    return run_host(ctx, kProdJvp, P, V, batch, dM, nullptr);
 }
 
 extern "C" int mcalf_model_jvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* ddM, void* stream) {
-    return deriv_device(ctx, true, dP, dV, batch, ddM, stream);
+    return run_device(ctx, kProdJvp, {dP, dV, ddM, nullptr}, batch, stream);
 }
 
 extern "C" int mcalf_model_vjp_batch(mcalf_ctx* ctx, const double* P, const double* Q, int64_t batch, double* G) {
-    return deriv_host(ctx, false, P, Q, batch, G);
+    return run_host(ctx, kProdVjp, P, Q, batch, G, nullptr);
 }
 
 extern "C" int mcalf_model_vjp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dQ, int64_t batch, double* dG, void* stream) {
-    return deriv_device(ctx, false, dP, dQ, batch, dG, stream);
+    return run_device(ctx, kProdVjp, {dP, dQ, dG, nullptr}, batch, stream);
 }
 
 extern "C" int mcalf_loglike_hvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dHV, void* stream) {
-    if (!ctx || batch < 0 || (batch > 0 && (!dP || !dV || !dHV))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
-    MCALF_SINGLE_ONLY(ctx, "mcalf_loglike_hvp_batch_device");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
-    return hvp_launch(ctx, dP, dV, batch, dHV, (hipStream_t)stream);
+    return run_device(ctx, kProdHvp, {dP, dV, dHV, nullptr}, batch, stream);
 }
 
 extern "C" int mcalf_loglike_hvp_batch(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* HV) {
-    if (!ctx || batch < 0 || (batch > 0 && (!P || !V || !HV))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
-    if (batch == 0) return MCALF_OK;
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, cut as the gradient's
-        struct HvpShard { const double *P, *V; double* HV; int ndim; } c = {P, V, HV, ctx->ndim};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const HvpShard* s = static_cast<const HvpShard*>(arg);
-            return mcalf_loglike_hvp_batch(static_cast<mcalf_ctx*>(sub), s->P + (size_t)lo * s->ndim, s->V + (size_t)lo * s->ndim, hi - lo,
-                                           s->HV + (size_t)lo * s->ndim);
-        }, &c);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t cells = (size_t)batch * ctx->ndim;
-    int rc;
-    if ((rc = grow(ctx, &ctx->g_P, &ctx->cap_g_P, cells))) return rc;
-    if ((rc = grow(ctx, &ctx->g_V, &ctx->cap_g_V, cells))) return rc;
-    if ((rc = grow(ctx, &ctx->g_G, &ctx->cap_g_G, cells))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_P, P, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->g_V, V, cells * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = hvp_launch(ctx, ctx->g_P, ctx->g_V, batch, ctx->g_G, ctx->stream))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(HV, ctx->g_G, cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->last.path = MCALF_PATH_HOST_STAGED;
-    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
-    ctx->last.pinned_out = is_pinned_host(HV) ? 1 : 0;
-    return MCALF_OK;
+    return run_host(ctx, kProdHvp, P, V, batch, HV, nullptr);
 }
 
 extern "C" int mcalf_voigt_hjerting_grad(const double* x, const double* y, int64_t n, double* out, int32_t device) {
@@ -338,7 +225,7 @@ extern "C" int mcalf_voigt_hjerting_grad(const double* x, const double* y, int64
     if (e == hipSuccess) {
         long cnt = (long)n;
         void* kargs[] = {(void*)&dx, (void*)&dy, (void*)&cnt, (void*)&dout};
-        e = hipLaunchKernel(grad_hjert_kernel_ptr(), dim3((unsigned)((n + 255) / 256)), dim3(256), kargs, 0, nullptr);
+        e = hipLaunchKernel(grad_kernel_ptr(kGradHjert), dim3((unsigned)((n + 255) / 256)), dim3(256), kargs, 0, nullptr);
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout, 3 * nb, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err(nullptr, MCALF_ERR_HIP, "hjerting_grad: %s", hipGetErrorString(e));

@@ -182,7 +182,7 @@ def test_smallest_parameter_layouts(ncomp, nfill):
 
 def test_more_rows_than_one_grid_y():
     """70 000 rows of the 64-pixel, 49-tap problem in one JVP call and one VJP call: two passes, of 65 535 and 4 465 rows
-    (grad_chunk_rows), whose offsets into V, dM, Q and G are jvp_launch's and vjp_launch's own.  Every row has the bits it
+    (grad_chunk_rows), whose offsets into V, dM, Q and G are the JVP's and the VJP's own (host_grad.cpp: bind).  Every row has the bits it
     has in a block of 4096, and 64 sampled rows -- both sides of the pass boundary among them -- match the reference."""
     kw = short_problem()
     prob = problem_from_kwargs(kw)
@@ -240,7 +240,7 @@ def _bits(t):
 
 
 def test_device_entries_leave_their_operands_alone():
-    """The VJP's pass reads the caller's cotangent through the q workspace pointer (a const_cast in vjp_launch): after the
+    """The VJP's pass reads the caller's cotangent through the q workspace pointer (a const_cast in host_grad.cpp: kProdVjp): after the
     device entries, on a side stream, dQ -- and dP, dV after the JVP -- hold the bits they held before."""
     kw = _civ(specres=(6.0, 9.0), contval=(0.9, 1.1))
     prob = problem_from_kwargs(kw)
