@@ -21,6 +21,8 @@
  *   mcalf_loglike_grad_batch <- jax.grad of the get_jax_likelihood closure  hires_fitter.py:521-695
  *                             (no counterpart on the numpy path: finite differences of lnlhood_worker)
  *   mcalf_loglike_hvp_batch  <- jax.jvp(jax.grad(...)) / jax.hessian of the same closure   hires_fitter.py:521-695
+ *   mcalf_eqw_batch        <- als_fitter.calc_w                       hires_fitter.py:467-491
+ *                             (every row of a chain at once, per component and per line, and the blended profile's width)
  *   mcalf_voigt_hjerting[_nodes] <- scipy.special.wofz(u + i a).real  hires_fitter.py:365
  *                             / voigt_jax.hjert                       voigt_jax.py:121-127
  *   mcalf_set_cu_mask, mcalf_stream_partition
@@ -77,7 +79,8 @@ extern "C" {
                                  9: mcalf_model_jvp_batch[_device], mcalf_model_vjp_batch[_device] (the model Jacobian's products
                                     with a vector)
                                     (added within 9, nothing else changed: mcalf_loglike_hvp_batch[_device], the product of
-                                    logL's exact Hessian with a vector) */
+                                    logL's exact Hessian with a vector;
+                                    mcalf_eqw_batch[_device], batched equivalent widths) */
 
 enum {
     MCALF_OK = 0,
@@ -360,6 +363,32 @@ int mcalf_loglike_hvp_batch(mcalf_ctx* ctx, const double* P, const double* V, in
 /* Same, device pointers, on the caller's stream (single-device contexts); dP and dV are only read.  After one call of the
  * same or a larger batch it allocates and synchronises nothing. */
 int mcalf_loglike_hvp_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dHV, void* stream);
+
+/* Equivalent widths of every row, on the device, without a spectrum reaching memory (the analysis pass over a chain:
+ * als_fitter.calc_w, hires_fitter.py:467-491).  P is batch x ndim.  With dlam[0] = wl[1] - wl[0], dlam[i] = wl[i] - wl[i-1]
+ * (:485-486) and tau_cl the optical depth of line l of the component in slot c alone (voigt_tau, :331-367):
+ *   Wcomp[i, c, l] = ( sum_pix (1 - exp(-tau_cl(pix))) dlam[pix] ) / (1 + z_c)      batch x ncompmax x nlines, rest frame, Angstrom
+ *   Wblend[i, l]   =   sum_pix (1 - exp(-sum_c tau_cl(pix))) dlam[pix]              batch x nlines, observed frame, Angstrom
+ * the second summed over the same slots: the width of the absorption system in line l, which overlapping components make
+ * smaller than sum_c (1 + z_c) Wcomp.  Either output may be NULL, not both.  Nothing is convolved (the periodic, normalised
+ * LSF does not change W) and the continuum does not enter (the reference's (cont v) / cont; the NaN it gives for a zero or
+ * non-finite continuum is the caller's to reproduce).  Fillers take no part.  The Voigt function is the likelihood's.
+ *   MCALF_EQW_LAYOUT      slot c reads (N, z, b) at startind + 1 + 3c for c below the row's active count -- int() of the
+ *                         ncomp slot on the numpy path, floor on the JAX path, clamped to [0, ncompmax], as the likelihood
+ *                         decodes it; the cells of the other slots are exactly 0 and their parameters are never read.
+ *   MCALF_EQW_AS_WRITTEN  all ncompmax slots, slot c reading (N, z, b) at startind + 3c: the reference as written (:481-482),
+ *                         its triples shifted by one against the layout.
+ * The conventions are the derivative entries': per-row numerical failures are values (a NaN in one row touches only that
+ * row); no atomics, every reduction in one fixed order, so a row's bits do not depend on its batch, its position, the pass it
+ * falls in, the outputs requested or the device count; a multi-device context cuts the rows as mcalf_loglike_grad_batch
+ * does.  MCALF_ERR_INVALID before any device work for: a NULL context, batch < 0, a NULL P with batch > 0, both outputs
+ * NULL, an indexing outside {0, 1}, a spectrum of fewer than 2 pixels (dlambda[0] needs two).  batch == 0 does nothing. */
+enum { MCALF_EQW_LAYOUT = 0, MCALF_EQW_AS_WRITTEN = 1 };
+int mcalf_eqw_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t indexing, double* Wcomp, double* Wblend);
+/* Same, device pointers, on the caller's stream (single-device contexts).  After one call of the same or a larger batch it
+ * allocates and synchronises nothing. */
+int mcalf_eqw_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, double* dWcomp, double* dWblend,
+                           void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -17,6 +17,8 @@ MCALF_ERR_INVALID, MCALF_ERR_HIP, MCALF_ERR_NODEVICE, MCALF_ERR_RANGE, MCALF_ERR
 MCALF_COMM_ID_BYTES = 128
 MCALF_CONV_WRAP_NUMPY = 0
 MCALF_CONV_SAME_EDGE_JAX = 1
+MCALF_EQW_LAYOUT = 0
+MCALF_EQW_AS_WRITTEN = 1
 
 _ERR_NAMES = {-1: "MCALF_ERR_INVALID", -2: "MCALF_ERR_HIP", -3: "MCALF_ERR_NODEVICE",
               -4: "MCALF_ERR_RANGE", -5: "MCALF_ERR_NOMEM", -6: "MCALF_ERR_COMM"}
@@ -142,6 +144,8 @@ SYMBOLS = {
     "mcalf_loglike_grad_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_loglike_hvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_loglike_hvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mcalf_eqw_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcalf_eqw_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

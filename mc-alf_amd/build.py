@@ -1,8 +1,9 @@
 """Build libmcalf_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is nine translation units: two device files -- kernels.hip (the likelihood's kernels) and grad_kernels.hip
-(the analytic gradient's and the Jacobian products') -- and the host side of the C ABI -- host_abi.cpp, host_stream.cpp, host_config.cpp,
-host_multi.cpp, host_grad.cpp, broker.cpp, comm.cpp -- compiled as plain C++ against the HIP runtime API.  Objects are
+The library is eleven translation units: three device files -- kernels.hip (the likelihood's kernels), grad_kernels.hip
+(the analytic gradient's and the Jacobian products') and eqw_kernels.hip (the equivalent widths') -- and the host side of the C ABI --
+host_abi.cpp, host_stream.cpp, host_config.cpp, host_multi.cpp, host_grad.cpp, host_eqw.cpp, broker.cpp, comm.cpp -- compiled as plain
+C++ against the HIP runtime API.  Objects are
 kept under csrc/obj/ so that an edit of a host file does not recompile the kernels (22 s), and an edit of the gradient's
 device files does not recompile the likelihood's."""
 from __future__ import annotations
@@ -15,14 +16,18 @@ import subprocess
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 KERNEL_SOURCE = "kernels.hip"
 GRAD_SOURCE = "grad_kernels.hip"
-DEVICE_SOURCES = [KERNEL_SOURCE, GRAD_SOURCE]
-HOST_SOURCES = ["host_abi.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "host_grad.cpp", "broker.cpp", "comm.cpp"]
+EQW_SOURCE = "eqw_kernels.hip"
+DEVICE_SOURCES = [KERNEL_SOURCE, GRAD_SOURCE, EQW_SOURCE]
+HOST_SOURCES = ["host_abi.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "host_grad.cpp", "host_eqw.cpp", "broker.cpp", "comm.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
 # what the DEVICE code is made of: the kernel-source hash covers exactly these
 HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h"]
 # the gradient's device object (not hashed: the fused kernel does not include these)
 GRAD_DEPS = ["grad_kernels.hip", "grad_args.h", "voigt_grad.h", "kernel_args.h", "voigt_tables.h"]
-HOST_HEADERS = ["host_ctx.h", "kernel_args.h", "grad_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
+# the equivalent widths' device object (its own sources are not hashed either; the Voigt function it shares with the fused kernel,
+# voigt_device.h and voigt_tables.h, is)
+EQW_DEPS = ["eqw_kernels.hip", "eqw_args.h", "voigt_device.h", "kernel_args.h", "voigt_tables.h"]
+HOST_HEADERS = ["host_ctx.h", "kernel_args.h", "grad_args.h", "eqw_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
 TARGET = os.path.join(CSRC, "libmcalf_hip.so")
 OBJDIR = os.path.join(CSRC, "obj")
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
@@ -41,7 +46,9 @@ def _mtime(name: str) -> float:
 def _deps(src: str):
     if src == KERNEL_SOURCE:
         return [src] + HASHED
-    return GRAD_DEPS if src == GRAD_SOURCE else [src] + HOST_HEADERS
+    if src in (GRAD_SOURCE, EQW_SOURCE):
+        return GRAD_DEPS if src == GRAD_SOURCE else EQW_DEPS
+    return [src] + HOST_HEADERS
 
 
 def _stale(target: str, deps) -> bool:
@@ -100,12 +107,16 @@ def build(force: bool = False, verbose: bool = False, testing: bool = False, tar
             fh.write(stamp)
         relinked = True
     objs.append(kobj)
-    # the gradient's kernel object (also shared by both variants)
-    gobj = os.path.join(OBJDIR, "grad_kernels.o")
-    if (force and not testing) or _stale(gobj, _deps(GRAD_SOURCE)):
-        _run([hipcc] + KERNEL_FLAGS + ["-c", GRAD_SOURCE, "-o", gobj], verbose)
-        relinked = True
-    objs.append(gobj)
+    # the gradient's and the equivalent widths' kernel objects (also shared by both variants)
+    for dsrc in (GRAD_SOURCE, EQW_SOURCE):
+        dobj = os.path.join(OBJDIR, os.path.splitext(dsrc)[0] + ".o")
+        if (force and not testing) or _stale(dobj, _deps(dsrc)):
+            cmd = [hipcc] + KERNEL_FLAGS + ["-c", dsrc, "-o", dobj]
+            if verbose and dsrc == EQW_SOURCE:
+                cmd.append("-Rpass-analysis=kernel-resource-usage")
+            _run(cmd, verbose)
+            relinked = True
+        objs.append(dobj)
     for src in HOST_SOURCES:
         obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
         # (host_abi.cpp carries the hash string: it is recompiled when the kernels changed)

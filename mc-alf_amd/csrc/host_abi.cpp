@@ -76,6 +76,7 @@ extern "C" void mcalf_destroy(mcalf_ctx* ctx) {
     if (ctx->res_stream) (void)hipStreamDestroy(ctx->res_stream);
     if (ctx->h_box) (void)hipHostFree((void*)ctx->h_box);
     if (ctx->d_res_shared) (void)hipFree(ctx->d_res_shared);
+    eqw_release(ctx);                                     // (dlam always exists: hipFree waits for the device, so only after the resident kernel was told to leave)
     void* bufs[] = {ctx->d_nu, ctx->d_obj, ctx->d_ispec2, ctx->d_lgis, ctx->d_err, ctx->d_tabs, ctx->d_lines, ctx->d_wtab, ctx->d_segok,
                     ctx->d_P,  ctx->d_out, ctx->d_partial, ctx->d_model, ctx->d_bounds, ctx->d_prior, ctx->d_recs, ctx->d_taps, ctx->d_hdr,
                     ctx->d_queue, ctx->d_order, ctx->d_sws, ctx->d_wide, ctx->d_wtaps, ctx->d_wpartial, ctx->d_wrows, ctx->d_whdr};
@@ -262,6 +263,7 @@ static int create_impl(const mcalf_spec* sp, mcalf_ctx* ctx) {
     HIP_TRY(ctx, hipMemcpy(ctx->d_lines, lines.data(), lines.size() * sizeof(LineDev), hipMemcpyHostToDevice));
     rc = upload_tables(ctx, &ctx->d_tabs);
     if (rc) return rc;
+    if ((rc = eqw_prepare(ctx, sp->wl))) return rc;
 
     // Far-wing interpolation set-up: which 64-pixel segments of each tile may be interpolated in
     // pixel-index space.  A segment qualifies when it lies inside the tile's extent without crossing

@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_stream.cpp, host_grad.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_stream.cpp, host_grad.cpp, host_eqw.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -268,6 +268,11 @@ struct mcalf_ctx {
     enum { kGbRows, kGbRecs, kGbTaps, kGbDtaps, kGbF, kGbQ, kGbPart, kGbShared, kGbDdtaps = kGbShared, kGbHq, kGbHdq, kGbHvp,
            kGbLogL = kGbHvp, kGbP, kGbV, kGbG, kGbX, kGbCount };
     struct GradBuf { double* p = nullptr; size_t cap = 0; } gb[kGbCount];
+    // The equivalent-width entries (host_eqw.cpp): the wavelength steps [npix] (hires_fitter.py:485-486; none for a one-pixel
+    // spectrum), the two per-row workspaces of one pass and the host-pointer entry's staging, grown on demand.
+    double* d_dlam = nullptr;
+    enum { kEbRecs, kEbPart, kEbP, kEbWcomp, kEbWblend, kEbCount };
+    GradBuf eb[kEbCount];
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -365,6 +370,10 @@ int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out);
 
 // ---- host_grad.cpp: the derivative entries ----------------------------------------------------------------------------
 void grad_release(mcalf_ctx* ctx);                     // frees every buffer of ctx->gb
+
+// ---- host_eqw.cpp: the equivalent-width entries -------------------------------------------------------------------------
+int eqw_prepare(mcalf_ctx* ctx, const double* wl);     // mcalf_create: dlam on the device
+void eqw_release(mcalf_ctx* ctx);                      // frees dlam and every buffer of ctx->eb
 
 // ---- comm.cpp -----------------------------------------------------------------------------------------------------------
 void comm_release(mcalf_ctx* ctx);

@@ -1,0 +1,135 @@
+// Host side of the equivalent-width kernels (eqw_kernels.hip): mcalf_eqw_batch and mcalf_eqw_batch_device.  One driver
+// (run_eqw) issues set-up, pixel pass and finalize pass by pass over row blocks whose per-row workspaces stay within
+// kGradChunkBytes and whose rows fit grid.y -- the derivative driver's rule (host_grad.cpp).  The wavelength steps dlam are a
+// device array of the context, computed once in mcalf_create with numpy's two steps (hires_fitter.py:485-486).
+#include "eqw_args.h"
+#include "grad_args.h"
+#include "host_ctx.h"
+
+static_assert(kEqwIndexLayout == MCALF_EQW_LAYOUT && kEqwIndexAsWritten == MCALF_EQW_AS_WRITTEN, "the kernels' indexing codes are the ABI's");
+
+namespace {
+
+int eqw_ntiles(const mcalf_ctx* ctx) { return (int)((ctx->npix + kEqwTile - 1) / kEqwTile); }
+int64_t eqw_nrec(const mcalf_ctx* ctx) { return (int64_t)ctx->ncompmax * ctx->nlines; }
+int64_t eqw_ncells(const mcalf_ctx* ctx) { return (int64_t)(ctx->ncompmax + 1) * ctx->nlines; }
+// doubles per row of the two per-row workspaces
+int64_t recs_row(const mcalf_ctx* ctx) { return std::max<int64_t>(1, eqw_nrec(ctx)) * kEqwRec; }
+int64_t part_row(const mcalf_ctx* ctx) { return (int64_t)eqw_ntiles(ctx) * eqw_ncells(ctx) * kEqwWaves; }
+
+// Rows per pass: the workspaces of a pass within kGradChunkBytes, and the row on grid.y of the pixel kernel.
+constexpr int64_t kEqwMaxRows = 65535;
+int64_t eqw_chunk_rows(const mcalf_ctx* ctx) {
+    const int64_t per_row = (recs_row(ctx) + part_row(ctx)) * (int64_t)sizeof(double);
+    return std::min<int64_t>(kEqwMaxRows, std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row));
+}
+
+int grow_buf(mcalf_ctx* ctx, int b, size_t elems) { return grow(ctx, &ctx->eb[b].p, &ctx->eb[b].cap, elems); }
+
+// Everything that is wrong with a call before any device work; `name` is the entry that reports it.
+int eqw_check(mcalf_ctx* ctx, const char* name, const double* P, int64_t batch, int32_t indexing, const double* Wcomp, const double* Wblend) {
+    if (batch < 0) return set_err(ctx, MCALF_ERR_INVALID, "%s: batch must be >= 0, got %lld", name, (long long)batch);
+    if (batch > 0 && !P) return set_err(ctx, MCALF_ERR_INVALID, "%s: P is NULL", name);
+    if (!Wcomp && !Wblend) return set_err(ctx, MCALF_ERR_INVALID, "%s: Wcomp and Wblend are both NULL", name);
+    if (indexing != MCALF_EQW_LAYOUT && indexing != MCALF_EQW_AS_WRITTEN)
+        return set_err(ctx, MCALF_ERR_INVALID, "%s: indexing must be MCALF_EQW_LAYOUT (0) or MCALF_EQW_AS_WRITTEN (1), got %d", name, indexing);
+    if (!ctx) return set_err(ctx, MCALF_ERR_INVALID, "%s: ctx is NULL", name);
+    if (ctx->npix < 2)
+        return set_err(ctx, MCALF_ERR_INVALID, "%s: npix = %ld, an equivalent width needs a spectrum of at least 2 pixels "
+                       "(dlambda[0] = wl[1] - wl[0], hires_fitter.py:485-486)", name, ctx->npix);
+    return MCALF_OK;
+}
+
+// The batch on `stream`, device pointers: the workspaces of one pass (grown once: a later call of as many rows or fewer
+// allocates nothing), then the three kernels pass by pass; every kernel takes the argument block by value.
+int run_eqw(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, double* dWcomp, double* dWblend, hipStream_t stream) {
+    if (batch <= 0) return MCALF_OK;
+    const int64_t chunk = eqw_chunk_rows(ctx);
+    const size_t rows = (size_t)std::min(batch, chunk);
+    int rc;
+    if ((rc = grow_buf(ctx, mcalf_ctx::kEbRecs, rows * (size_t)recs_row(ctx))) || (rc = grow_buf(ctx, mcalf_ctx::kEbPart, rows * (size_t)part_row(ctx))))
+        return rc;
+    EqwArgs a = {};
+    a.nu = ctx->d_nu; a.dlam = ctx->d_dlam; a.lines = ctx->d_lines; a.tabs = ctx->d_tabs;
+    a.recs = ctx->eb[mcalf_ctx::kEbRecs].p; a.part = ctx->eb[mcalf_ctx::kEbPart].p;
+    a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = eqw_ntiles(ctx); a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax;
+    a.startind = ctx->startind; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0; a.indexing = indexing;
+    const size_t nrec = (size_t)eqw_nrec(ctx), ncells = (size_t)eqw_ncells(ctx);
+    for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
+        a.P = dP + (size_t)row0 * ctx->ndim;
+        a.Wcomp = dWcomp ? dWcomp + (size_t)row0 * nrec : nullptr;
+        a.Wblend = dWblend ? dWblend + (size_t)row0 * ctx->nlines : nullptr;
+        a.nrows = (int)std::min(chunk, batch - row0);
+        void* args[] = {(void*)&a};
+        HIP_TRY(ctx, hipLaunchKernel(eqw_kernel_ptr(kEqwSetup), dim3((unsigned)a.nrows), dim3(64), args, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel(eqw_kernel_ptr(kEqwPixel), dim3((unsigned)a.ntiles, (unsigned)a.nrows), dim3(kEqwBlock), args, 0, stream));
+        HIP_TRY(ctx, hipLaunchKernel(eqw_kernel_ptr(kEqwFinalize), dim3((unsigned)(((size_t)a.nrows * ncells + 255) / 256)), dim3(256), args, 0, stream));
+    }
+    return MCALF_OK;
+}
+
+struct HostShard { const double* P; int32_t indexing; double *Wcomp, *Wblend; int64_t ndim, nrec, nlines; };
+
+int run_host(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t indexing, double* Wcomp, double* Wblend) {
+    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
+        HostShard c = {P, indexing, Wcomp, Wblend, ctx->ndim, eqw_nrec(ctx), ctx->nlines};
+        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
+            const HostShard* s = static_cast<const HostShard*>(arg);
+            return run_host(static_cast<mcalf_ctx*>(sub), s->P + (size_t)lo * s->ndim, hi - lo, s->indexing,
+                            s->Wcomp ? s->Wcomp + (size_t)lo * s->nrec : nullptr, s->Wblend ? s->Wblend + (size_t)lo * s->nlines : nullptr);
+        }, &c);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nP = (size_t)batch * ctx->ndim, nC = Wcomp ? (size_t)batch * (size_t)eqw_nrec(ctx) : 0, nB = Wblend ? (size_t)batch * ctx->nlines : 0;
+    int rc;
+    if ((rc = grow_buf(ctx, mcalf_ctx::kEbP, nP)) || (rc = grow_buf(ctx, mcalf_ctx::kEbWcomp, nC)) || (rc = grow_buf(ctx, mcalf_ctx::kEbWblend, nB))) return rc;
+    const mcalf_ctx::GradBuf* eb = ctx->eb;
+    double* dC = nC ? eb[mcalf_ctx::kEbWcomp].p : nullptr;
+    double* dB = Wblend ? eb[mcalf_ctx::kEbWblend].p : nullptr;
+    HIP_TRY(ctx, hipMemcpyAsync(eb[mcalf_ctx::kEbP].p, P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_eqw(ctx, eb[mcalf_ctx::kEbP].p, batch, indexing, dC, dB, ctx->stream))) return rc;
+    if (nC) HIP_TRY(ctx, hipMemcpyAsync(Wcomp, dC, nC * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (nB) HIP_TRY(ctx, hipMemcpyAsync(Wblend, dB, nB * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->last.path = MCALF_PATH_HOST_STAGED;
+    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
+    ctx->last.pinned_out = is_pinned_host(Wcomp ? Wcomp : Wblend) ? 1 : 0;
+    return MCALF_OK;
+}
+
+}  // namespace
+
+// dlam[0] = wl[1] - wl[0], dlam[i] = wl[i] - wl[i-1]: np.diff, then np.insert(d, 0, d[0]) (hires_fitter.py:485-486).  A
+// one-pixel spectrum has none (the entries refuse it).
+int eqw_prepare(mcalf_ctx* ctx, const double* wl) {
+    if (ctx->npix < 2) return MCALF_OK;
+    std::vector<double> dlam((size_t)ctx->npix);
+    for (long i = 1; i < ctx->npix; ++i) dlam[i] = wl[i] - wl[i - 1];
+    dlam[0] = dlam[1];
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_dlam, dlam.size() * sizeof(double)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_dlam, dlam.data(), dlam.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MCALF_OK;
+}
+
+void eqw_release(mcalf_ctx* ctx) {
+    if (ctx->d_dlam) (void)hipFree(ctx->d_dlam);
+    for (mcalf_ctx::GradBuf& b : ctx->eb)
+        if (b.p) (void)hipFree(b.p);
+}
+
+extern "C" int mcalf_eqw_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t indexing, double* Wcomp, double* Wblend) {
+    const int rc = eqw_check(ctx, "mcalf_eqw_batch", P, batch, indexing, Wcomp, Wblend);
+    if (rc || batch == 0) return rc;
+    return run_host(ctx, P, batch, indexing, Wcomp, Wblend);
+}
+
+extern "C" int mcalf_eqw_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, double* dWcomp, double* dWblend,
+                                      void* stream) {
+    const int rc = eqw_check(ctx, "mcalf_eqw_batch_device", dP, batch, indexing, dWcomp, dWblend);
+    if (rc) return rc;
+    MCALF_SINGLE_ONLY(ctx, "mcalf_eqw_batch_device");
+    if (batch == 0) return MCALF_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    return run_eqw(ctx, dP, batch, indexing, dWcomp, dWblend, (hipStream_t)stream);
+}

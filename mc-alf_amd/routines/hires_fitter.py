@@ -554,6 +554,85 @@ class als_fitter:
                                                  out.ctypes.data_as(pd)), self._ctx)
         return out
 
+    # ------------------------------------------------------------------ batched analysis pass
+    def eqw_batch(self, P, reference_indexing=False, out=None, comp=True, blend=True):
+        """Equivalent widths of every row on the device (HIP kernels; no spectrum is written to memory):
+        `(Wcomp[batch, ncompmax, nlines], Wblend[batch, nlines])`, in Angstrom.
+
+        `Wcomp[i, c, l]` is the rest-frame width of line `l` of the component in slot `c` alone -- the term `calc_w` sums
+        (hires_fitter.py:488-489).  `Wblend[i, l]` is the observed-frame width of line `l` of all the row's slots TOGETHER,
+        sum_pix (1 - exp(-sum_c tau_cl)) dlambda: where components overlap it is smaller than sum_c (1 + z_c) Wcomp[i, c, l].
+        Nothing is convolved (the LSF does not change W) and the continuum does not enter.
+
+        `reference_indexing=False`: slot `c` reads (N, z, b) at `startind + 1 + 3c` for `c` below the row's active count
+        (clamped to [0, ncompmax] as the likelihood does); the other cells are exactly 0 and a NaN there does not leak.
+        `reference_indexing=True`: all `ncompmax` slots, read from `startind + 3c` -- the reference as written (:481-482).
+        `comp=False` / `blend=False` leave that output out (None is returned in its place); `out=(Wcomp, Wblend)` (float64,
+        C-contiguous; an entry may be None) is filled in place.  A row's bits depend on nothing but the row."""
+        P = self._rows(P, self.ndim)
+        n = P.shape[0]
+        shapes = ((n, int(self.ncompmax), self.numlines), (n, self.numlines))
+        res = []
+        for k, (want, shape) in enumerate(zip((comp, blend), shapes)):
+            arr = None if out is None else out[k]
+            if not want:
+                arr = None
+            elif arr is None:
+                arr = np.empty(shape)
+            elif arr.dtype != np.float64 or not arr.flags.c_contiguous or arr.size != int(np.prod(shape)):
+                raise ValueError(f"out[{k}] must be a C-contiguous float64 array of shape {list(shape)}")
+            res.append(arr)
+        if res[0] is None and res[1] is None:
+            raise ValueError("eqw_batch: at least one of comp / blend must be requested")
+        rc = self._lib.mcalf_eqw_batch(self._ctx, self._ptr(P), n, _lib.MCALF_EQW_AS_WRITTEN if reference_indexing else _lib.MCALF_EQW_LAYOUT,
+                                       None if res[0] is None else self._ptr(res[0]), None if res[1] is None else self._ptr(res[1]))
+        if rc:
+            _lib.check(rc, self._ctx)
+        return tuple(a if a is None or a.shape == shape else a.reshape(shape) for a, shape in zip(res, shapes))
+
+    def calc_w_batch(self, P, lineid=0, reference_indexing=True):
+        """`calc_w(P[i], lineid, reference_indexing)` for every row of a chain in one call: `eqw_batch`'s per-component
+        widths of line `lineid` summed over the slots in slot order ([batch], Angstrom).  Rows whose continuum is zero or
+        not finite are NaN, as the reference's `absorption / cont` (:488) makes them -- unless no slot is in use, where
+        `calc_w` returns 0 before it divides."""
+        P = self._rows(P, self.ndim)
+        lineid = int(lineid)
+        if not 0 <= lineid < self.numlines:
+            raise ValueError(f"lineid must be in [0, {self.numlines}), got {lineid}")
+        wcomp, _ = self.eqw_batch(P, reference_indexing=reference_indexing, blend=False)
+        w = np.zeros(P.shape[0])
+        for c in range(int(self.ncompmax)):
+            w += wcomp[:, c, lineid]
+        if reference_indexing:
+            used = np.full(P.shape[0], int(self.ncompmax) > 0)
+        else:
+            with np.errstate(invalid="ignore"):
+                used = (np.trunc(P[:, self.startind]) >= 1.0) & (int(self.ncompmax) > 0)
+        if self.freecont:
+            cont = P[:, 1 if self.freespecres else 0]
+        else:
+            cont = np.full(P.shape[0], _scalar(self.contval), dtype=float)
+        w[used & ~(np.isfinite(cont) & (cont != 0))] = np.nan
+        return w
+
+    def calc_N_batch(self, P):
+        """`calc_N(P[i], reference_indexing=False)` for every row ([batch]; host numpy, no kernel): log10 of the summed
+        columns of the slots with z < 10.  Rows that keep the same slots are summed together, each over exactly the entries
+        `calc_N` sums and in its order, so the values agree bit for bit."""
+        P = self._rows(P, self.ndim)
+        allN = P[:, self.startind + 1::3]
+        allz = P[:, self.startind + 2::3]
+        k = min(allN.shape[1], allz.shape[1])
+        allN, keep = allN[:, :k], allz[:, :k] < 10
+        out = np.empty(P.shape[0])
+        masks, which = np.unique(keep, axis=0, return_inverse=True)
+        which = np.asarray(which).reshape(-1)
+        with np.errstate(divide="ignore"):
+            for m, mask in enumerate(masks):
+                rows = np.flatnonzero(which == m)
+                out[rows] = np.log10(np.sum(10 ** np.ascontiguousarray(allN[rows][:, mask]), axis=1))
+        return out
+
     # ------------------------------------------------------------------ reference callables
     def _check_scalar(self, p):
         """The single-point callables of the reference raise where Python's `int()` does: a NaN or
