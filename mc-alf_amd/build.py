@@ -1,8 +1,9 @@
 """Build libmcalf_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is eleven translation units: three device files -- kernels.hip (the likelihood's kernels), grad_kernels.hip
+The library is fourteen translation units: three device files -- kernels.hip (the likelihood's kernels), grad_kernels.hip
 (the analytic gradient's and the Jacobian products') and eqw_kernels.hip (the equivalent widths') -- and the host side of the C ABI --
-host_abi.cpp, host_stream.cpp, host_config.cpp, host_multi.cpp, host_grad.cpp, host_eqw.cpp, broker.cpp, comm.cpp -- compiled as plain
+host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_config.cpp, host_multi.cpp, host_grad.cpp, host_eqw.cpp,
+broker.cpp, comm.cpp -- compiled as plain
 C++ against the HIP runtime API.  Objects are
 kept under csrc/obj/ so that an edit of a host file does not recompile the kernels (22 s), and an edit of the gradient's
 device files does not recompile the likelihood's."""
@@ -18,7 +19,7 @@ KERNEL_SOURCE = "kernels.hip"
 GRAD_SOURCE = "grad_kernels.hip"
 EQW_SOURCE = "eqw_kernels.hip"
 DEVICE_SOURCES = [KERNEL_SOURCE, GRAD_SOURCE, EQW_SOURCE]
-HOST_SOURCES = ["host_abi.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "host_grad.cpp", "host_eqw.cpp", "broker.cpp", "comm.cpp"]
+HOST_SOURCES = ["host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "host_grad.cpp", "host_eqw.cpp", "broker.cpp", "comm.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
 # what the DEVICE code is made of: the kernel-source hash covers exactly these
 HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h"]

@@ -23,11 +23,11 @@ bool resident_serves(const mcalf_ctx* ctx, int mode, int64_t batch, int rowlen, 
 // One theta through the resident kernel: post the request (launching the kernel when there is none), spin on the result.
 int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out) {
     if (!ctx->h_box) {
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_box, sizeof(ResidentBox), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_box.p, sizeof(ResidentBox), hipHostMallocMapped | hipHostMallocCoherent));
         std::memset((void*)ctx->h_box, 0, sizeof(ResidentBox));
         HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->d_box, (void*)ctx->h_box, 0));
         { const int rcs = create_stream(ctx, &ctx->res_stream); if (rcs) return rcs; }      // (with the context's CU mask, when it has one)
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_res_shared, sizeof(ResidentShared)));
+        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_res_shared.p, sizeof(ResidentShared)));
         const void* k = resident_kernel_ptr(ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX, ctx->selfhalo != 0);
         HIP_TRY(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsBudget + 1024)));
     }
@@ -36,12 +36,12 @@ int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out) {
     __atomic_store_n(res, kResultPending, __ATOMIC_RELAXED);
     std::memcpy(box->row, row, (size_t)rowlen * sizeof(double));
     const unsigned seq = ++ctx->res_seq;
-    ctx->last.path = MCALF_PATH_HOST_ZEROCOPY; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    set_path(ctx, MCALF_PATH_HOST_ZEROCOPY, false, false);
     ctx->last.persistent = 0; ctx->last.grid = 1; ctx->last.items = 1; ctx->last.inline_setup = 3; ctx->last.stream_polled = 1;
     ctx->res_calls++;
     auto launch_kernel = [&]() -> int {
         // (a previous kernel of this context has said "gone", or there was none: a new one starts behind it on the stream)
-        KArgs a = make_kargs(ctx, kModeLogL, nullptr, 0, 1, 0, 0, 0, nullptr, nullptr, false, nullptr);
+        KArgs a = make_kargs(ctx, LaunchReq(kModeLogL, nullptr, 1, nullptr), 0, 1, 0);
         a.persist = 0; a.order = nullptr;
         __atomic_store_n(&box->state, kResRunning, __ATOMIC_RELAXED);
         __atomic_store_n(&box->quit, 0u, __ATOMIC_RELAXED);
@@ -200,8 +200,10 @@ extern "C" int mcalf_broker_serve(mcalf_ctx* const* ctxs, int32_t nctx, const mc
                 uint64_t* res = reinterpret_cast<uint64_t*>(L.c->h_small + kSmallDoubles);
                 for (int i = 0; i < L.n; ++i) __atomic_store_n(res + i, kPending, __ATOMIC_RELEASE);
                 L.polls = 0;
-                L.c->last.path = MCALF_PATH_HOST_ZEROCOPY; L.c->last.pinned_in = L.c->last.pinned_out = 0;
-                if ((rc = launch(L.c, kModeLogL, L.c->d_small, L.n, 0, 0, L.c->d_small + kSmallDoubles, nullptr, L.c->stream))) {
+                begin_call(L.c, MCALF_PATH_HOST_ZEROCOPY, false, false);
+                LaunchReq q(kModeLogL, L.c->d_small, L.n, L.c->stream);
+                q.d_out = L.c->d_small + kSmallDoubles;
+                if ((rc = launch(L.c, q))) {
                     for (int k = 0; k < nctx; ++k)
                         if (lane[k].busy) (void)hipStreamSynchronize(lane[k].c->stream);
                     return rc;
@@ -270,7 +272,7 @@ extern "C" int mcalf_broker_serve_resident(mcalf_ctx* ctx, void* boxes, int32_t 
             // about to end.  Only when the launch has ended is another one started.
             const hipError_t q = launched ? hipStreamQuery(st) : hipSuccess;
             if (q == hipSuccess) {
-                KArgs a = make_kargs(ctx, kModeLogL, nullptr, 0, 1, 0, 0, 0, nullptr, nullptr, false, nullptr);
+                KArgs a = make_kargs(ctx, LaunchReq(kModeLogL, nullptr, 1, nullptr), 0, 1, 0);
                 a.persist = 0; a.order = nullptr;
                 for (int s = 0; s < slots; ++s) __atomic_store_n(&hb[s].state, kResRunning, __ATOMIC_RELEASE);
                 long long idle = (long long)idle_us * 100;

@@ -186,7 +186,9 @@ extern "C" int mcalf_loglike_gatherv_device(mcalf_ctx* ctx, const double* dP, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)batch_local;
-    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    begin_call(ctx, MCALF_PATH_DEVICE, false, false);
+    LaunchReq q(kModeLogL, dP, batch_local, st);
+    q.d_out = dlogL_local;
 
     // ---- 2. everything that can fail locally, BEFORE anything is enqueued ---------------------------------
     // A rank that fails here (or in the kernel launches below) still takes its part in the exchange, with a block
@@ -210,7 +212,7 @@ extern "C" int mcalf_loglike_gatherv_device(mcalf_ctx* ctx, const double* dP, in
             return comm_fail(ctx, "hipStreamWaitEvent", ncclSystemError);
     }
     // ---- 3. kernels ------------------------------------------------------------------------------------------
-    if (rc_local == MCALF_OK && n > 0) rc_local = launch(ctx, kModeLogL, dP, batch_local, 0, 0, dlogL_local, nullptr, st);
+    if (rc_local == MCALF_OK && n > 0) rc_local = launch(ctx, q);
     const std::string local_msg = ctx->err;
     if (rc_local != MCALF_OK && n > 0) (void)hipMemsetAsync(dlogL_local, 0xFF, n * sizeof(double), st);   // NaN block
     // ---- 4. exchange -----------------------------------------------------------------------------------------

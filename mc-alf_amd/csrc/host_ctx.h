@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_stream.cpp, host_grad.cpp, host_eqw.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_eqw.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -36,7 +36,7 @@ constexpr int64_t kStreamTiledMaxItems = 65536;   // tiled spectra stream up to 
 using namespace mcalf;
 
 // A persistent helper thread of a context (the other devices of a multi-device context: host_multi.cpp; the staging copy
-// of a large pageable batch: host_abi.cpp).  One job at a time: post(), then wait().  The thread looks for the next job
+// of a large pageable batch: host_pipeline.cpp).  One job at a time: post(), then wait().  The thread looks for the next job
 // for a short while after one -- a sampler calls back to back -- and then sleeps on a condition variable.
 typedef int (*WorkFn)(void* who, int64_t lo, int64_t hi, void* arg);
 struct HostWorker {
@@ -135,6 +135,21 @@ struct HostTrace { double stage_us = 0, stage_bytes = 0, helper_bytes = 0, helpe
 struct BlockTimeline { int n = 0; long rows[kMaxChunks]; float h2d0[kMaxChunks], h2d1[kMaxChunks], done[kMaxChunks]; double host_enq[kMaxChunks], call_h2d[kMaxChunks], call_order[kMaxChunks], call_launch[kMaxChunks]; int pinned = 0; double sync_us = 0; };
 struct StreamTrace { double t[6] = {}; long n = 0; };
 
+// A buffer the context owns: device memory (hipFree) or a page-locked host block (kPinned: hipHostFree), with its capacity in
+// elements.  It reads as the plain pointer wherever one is wanted and is released when the context is deleted -- in
+// mcalf_destroy that is after the resident kernel has been told to leave (hipFree waits for the device).
+template <typename T, bool kPinned = false>
+struct DevBuf {
+    T* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)(kPinned ? hipHostFree((void*)p) : hipFree((void*)p)); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+template <typename T> using PinBuf = DevBuf<T, true>;
+
 struct mcalf_ctx {
     HostTrace htrace;
     BlockTimeline btrace;
@@ -155,16 +170,13 @@ struct mcalf_ctx {
     size_t lds_bytes = 0, lds_bytes_inline = 0;    // (the one-launch variant of small calls folds 4 lines per barrier)
     int inline_max_items = 0;                      // launches of at most this many work items take the one-launch variant
     // device buffers
-    double *d_nu = nullptr, *d_obj = nullptr, *d_ispec2 = nullptr, *d_lgis = nullptr, *d_err = nullptr, *d_tabs = nullptr;
-    LineDev* d_lines = nullptr;
-    double* d_wtab = nullptr;
-    unsigned long long* d_segok = nullptr;
+    DevBuf<double> d_nu, d_obj, d_ispec2, d_lgis, d_err, d_tabs, d_wtab;
+    DevBuf<LineDev> d_lines;
+    DevBuf<unsigned long long> d_segok;
     double dnu_seg = 0;
     // workspaces (grown on demand)
-    double *d_P = nullptr, *d_out = nullptr, *d_partial = nullptr, *d_model = nullptr, *d_bounds = nullptr, *d_prior = nullptr;
-    double *d_recs = nullptr, *d_taps = nullptr;
-    SampleHdr* d_hdr = nullptr;
-    size_t cap_P = 0, cap_out = 0, cap_partial = 0, cap_model = 0, cap_recs = 0, cap_taps = 0, cap_hdr = 0;
+    DevBuf<double> d_P, d_out, d_partial, d_model, d_bounds, d_prior, d_recs, d_taps;
+    DevBuf<SampleHdr> d_hdr;
     hipStream_t stream = nullptr;
     // optional per-launch timing of the fused kernel (mcalf_profile_begin / _end)
     std::vector<hipEvent_t> ev;
@@ -174,16 +186,16 @@ struct mcalf_ctx {
     // page-locked, device-mapped staging block that the kernels read / write directly -- no copy commands.
     // Resident one-theta evaluator (mcalf_set_resident; off by default): its mailbox, its own stream, what the host
     // believes about the kernel, the next request number
-    ResidentBox* h_box = nullptr;       // page-locked, coherent, device-mapped
-    ResidentBox* d_box = nullptr;
-    ResidentShared* d_res_shared = nullptr;   // device words of the evaluator's launch (idle clock, leave flag)
+    PinBuf<ResidentBox> h_box;          // page-locked, coherent, device-mapped
+    ResidentBox* d_box = nullptr;       // the same memory as the device sees it
+    DevBuf<ResidentShared> d_res_shared;      // device words of the evaluator's launch (idle clock, leave flag)
     hipStream_t res_stream = nullptr;
     int resident_us = 0;                // idle limit in microseconds; 0 = no resident kernel
     bool res_alive = false;
     unsigned res_seq = 0;
     long res_launches = 0, res_calls = 0;
     std::vector<double> h_prior;        // the prior box as mcalf_set_prior took it: lo[ndim], hi[ndim] (host copy)
-    double* h_small = nullptr;          // host address
+    PinBuf<double> h_small;             // host address
     double* d_small = nullptr;          // the same memory as the device sees it
     // prior box of mcalf_set_prior (device copy in d_prior: lo[ndim] then hi[ndim])
     bool prior_set = false;
@@ -201,9 +213,8 @@ struct mcalf_ctx {
     int num_cu = 256;
     int persist = 1;                    // fused kernel as a persistent grid (MCALF_PERSIST=0: one workgroup per item)
     int setup_block = 512;              // threads per workgroup of the set-up kernel (MCALF_SETUP_BLOCK: 64 .. 512)
-    unsigned int* d_queue = nullptr;    // [kMaxChunks] work-item queues of the persistent kernel
-    int* d_order = nullptr;             // [batch] hand-out order of the persistent kernel (per row block)
-    size_t cap_order = 0;
+    DevBuf<unsigned int> d_queue;       // [kMaxChunks] work-item queues of the persistent kernel
+    DevBuf<int> d_order;                // [batch] hand-out order of the persistent kernel (per row block)
     int ordered = 1;                    // MCALF_ORDER=0: hand the live points out in row order
     hipStream_t aux[kMaxChunks - 1] = {};
     hipEvent_t ev_fork = nullptr, ev_join[kMaxChunks - 1] = {};
@@ -222,20 +233,20 @@ struct mcalf_ctx {
     bool fail_preflight = false;            // MCALF_TEST_FAIL_PREFLIGHT=1 (test builds only): an injected workspace-growth failure
 #endif
     // page-locked staging of the host-pointer entries: parameter rows in, scalars out
-    double* h_stage = nullptr;
-    size_t cap_stage = 0;
+    PinBuf<double> h_stage;
     // Streaming single launch of the host-pointer entries (run_host_stream): queues / stamps in HBM, the words the host
     // and the kernel exchange in a page-locked, device-mapped block (h_ctl: [0] status, [1] generation of the last
     // launch that has drained, [16] rows staged so far -- a cache line of its own)
-    // (ONE allocation: records, taps, parameter rows, headers, stamps of `cap_sws` live points, then the queues)
-    void* d_sws = nullptr;
-    size_t cap_sws = 0;
+    // (ONE allocation, carved up by hand: records, taps, parameter rows, headers, stamps of `sws_rows` live points, then the
+    // queues; its capacity counts live points, not elements)
+    DevBuf<void> d_sws;
+    size_t sws_rows = 0;
     double *s_recs = nullptr, *s_taps = nullptr, *s_P = nullptr;
     size_t s_rec_stride = 0, s_tap_stride = 0, s_hdr_stride = 0;
     SampleHdr* s_hdr = nullptr;
     StreamCtl* d_sctl = nullptr;
     unsigned int* d_ready = nullptr;
-    volatile unsigned int* h_ctl = nullptr;
+    PinBuf<volatile unsigned int> h_ctl;
     unsigned int* d_ctl = nullptr;          // the same words as the device sees them
     unsigned int stream_gen = 0;            // stamp of the last streaming launch; never restarts (a regrown workspace is zero-filled, and
                                             // a restarted count could meet the completion word of an earlier launch: h_ctl[1])
@@ -255,24 +266,23 @@ struct mcalf_ctx {
     int stream_poll = 1;                    // MCALF_STREAM_POLL=0: wait for the stream's signal instead of polling h_ctl[1]
     double stream_timeout_s = 0.5;          // MCALF_STREAM_TIMEOUT: longest wait of a wave inside the kernel
     // LSF wider than a workgroup tile (numpy boundary): the fused kernel runs WITHOUT convolution and continuum into
-    // d_wide, two more kernels do taps, periodic convolution, continuum and terms from HBM (host_abi.cpp: launch_wide).
+    // d_wide, two more kernels do taps, periodic convolution, continuum and terms from HBM (host_wide.cpp: launch_wide).
     // n_cap is 0 for such a context (the tile carries no halo); wide_n_cap is the half-width provisioned from specres_max.
     int wide = 0, wide_n_cap = 0;
-    double *d_wide = nullptr, *d_wtaps = nullptr, *d_wpartial = nullptr, *d_wrows = nullptr;
-    SampleHdr* d_whdr = nullptr;
-    size_t cap_wide = 0, cap_wtaps = 0, cap_wpartial = 0, cap_wrows = 0, cap_whdr = 0;
+    DevBuf<double> d_wide, d_wtaps, d_wpartial, d_wrows;
+    DevBuf<SampleHdr> d_whdr;
     mcalf_launch_info_t last = {};      // what the last call did (mcalf_last_launch)
     // The derivative entries' device buffers (host_grad.cpp), all grown on demand: the per-row workspaces of one pass -- the
     // seven every product shares, then the HVP's three -- and the rows of a batch: logL, and the host-pointer entries' staging
     // (parameters, tangents, gradients or H v, pixel rows).
     enum { kGbRows, kGbRecs, kGbTaps, kGbDtaps, kGbF, kGbQ, kGbPart, kGbShared, kGbDdtaps = kGbShared, kGbHq, kGbHdq, kGbHvp,
            kGbLogL = kGbHvp, kGbP, kGbV, kGbG, kGbX, kGbCount };
-    struct GradBuf { double* p = nullptr; size_t cap = 0; } gb[kGbCount];
+    DevBuf<double> gb[kGbCount];
     // The equivalent-width entries (host_eqw.cpp): the wavelength steps [npix] (hires_fitter.py:485-486; none for a one-pixel
     // spectrum), the two per-row workspaces of one pass and the host-pointer entry's staging, grown on demand.
-    double* d_dlam = nullptr;
+    DevBuf<double> d_dlam;
     enum { kEbRecs, kEbPart, kEbP, kEbWcomp, kEbWblend, kEbCount };
-    GradBuf eb[kEbCount];
+    DevBuf<double> eb[kEbCount];
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -294,14 +304,12 @@ void set_last_error(const std::string& msg);          // the thread's message (m
             return set_err(ctx, MCALF_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));  \
     } while (0)
 
-template <typename T>
-inline int grow(mcalf_ctx* ctx, T** ptr, size_t* cap, size_t need_elems) {
-    if (need_elems <= *cap) return MCALF_OK;
-    if (*ptr) HIP_TRY(ctx, hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)ptr, need_elems * sizeof(T)));
-    *cap = need_elems;
+template <typename T> inline int grow(mcalf_ctx* ctx, DevBuf<T>& buf, size_t need_elems) {
+    if (need_elems <= buf.cap) return MCALF_OK;
+    if (buf.p) HIP_TRY(ctx, hipFree(buf.p));
+    buf.p = nullptr; buf.cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&buf.p, need_elems * sizeof(T)));
+    buf.cap = need_elems;
     return MCALF_OK;
 }
 
@@ -311,17 +319,41 @@ inline double now_us() {
     return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
 }
 
-// The kernel arguments of rows [row0, row0 + nrows) of a batch (everything but the launch geometry).
-// wide_stage (contexts whose LSF is wider than a tile, launch_wide): which of the launch's kernels the block is for
-enum { kWideNone = 0, kWideFused = 1, kWideKernels = 2 };
-KArgs make_kargs(const mcalf_ctx* ctx, int mode, const double* dP, int64_t row0, int64_t nrows, int chunk, int targonly,
-                 int onecomp_fill, double* d_out, double* d_model, bool from_cube, double* d_theta, int wide_stage = kWideNone);
-// Enqueue one batch on `stream` (asynchronous): set-up kernel, fused kernel, finalize when tiled.
-int launch(mcalf_ctx* ctx, int mode, const double* dP, int64_t batch, int targonly, int onecomp_fill, double* d_out,
-           double* d_model, hipStream_t stream, bool from_cube = false, double* d_theta = nullptr);
-// Everything of a launch that can fail WITHOUT anything having been enqueued (range check, workspace growth).
-int launch_preflight(mcalf_ctx* ctx, int mode, int64_t batch);
-int launch_finalize(mcalf_ctx* ctx, const KArgs& a, int64_t nrows, int mode, hipStream_t stream, int nparts = 0, bool signal = false);
+inline bool mode_reduces(int mode) { return mode == kModeLogL || mode == kModeChi2; }   // one scalar per live point (else pixel rows)
+
+// One batch for the kernels: the mode, the rows as the DEVICE addresses them, where the results go, the stream.  from_cube: dP
+// holds unit-cube rows, mapped through the prior box while decoding; d_theta (optional) receives the transformed rows.
+struct LaunchReq {
+    int mode; const double* dP; int64_t batch; hipStream_t stream;
+    int targonly = 0, onecomp_fill = 0;
+    double *d_out = nullptr, *d_model = nullptr, *d_theta = nullptr;
+    bool from_cube = false;
+    LaunchReq(int mode_, const double* dP_, int64_t batch_, hipStream_t stream_) : mode(mode_), dP(dP_), batch(batch_), stream(stream_) {}
+    bool reduces() const { return mode_reduces(mode); }
+    int rowlen(const mcalf_ctx* ctx) const { return mode == kModeOneComp ? 5 : ctx->ndim; }
+};
+// One call of a host-pointer entry: the caller's rows and arrays.  theta_out (from_cube only, optional): the transformed rows.
+struct HostReq {
+    int mode; const double* P; int64_t batch; int rowlen;
+    int targonly = 0, fill = 0;
+    double *out_scalar = nullptr, *out_model = nullptr;
+    bool from_cube = false; double* theta_out = nullptr;
+    bool reduces() const { return mode_reduces(mode); }
+    // the same request on device rows (the outputs are the plan's to set)
+    LaunchReq on_device(const double* dP, hipStream_t stream) const {
+        LaunchReq q(mode, dP, batch, stream);
+        q.targonly = targonly; q.onecomp_fill = fill; q.from_cube = from_cube;
+        return q;
+    }
+};
+
+// The launch record of a call (mcalf_last_launch): every entry starts it from zero, so that no field of an earlier call
+// survives; the plan that ends up evaluating a host-pointer call names itself with set_path.
+inline void set_path(mcalf_ctx* ctx, int path, bool pinned_in, bool pinned_out) {
+    ctx->last.path = path; ctx->last.pinned_in = pinned_in ? 1 : 0; ctx->last.pinned_out = pinned_out ? 1 : 0;
+}
+inline void begin_call(mcalf_ctx* ctx, int path, bool pinned_in, bool pinned_out) { ctx->last = mcalf_launch_info_t(); set_path(ctx, path, pinned_in, pinned_out); }
+
 int ensure_small(mcalf_ctx* ctx);                      // the page-locked block of small calls
 int pick_device(mcalf_ctx* ctx, int requested, int* out_dev, std::string* arch);   // a usable gfx950 device (-1: the current one)
 bool is_pinned_host(const void* p);
@@ -337,6 +369,35 @@ void apply_environment(mcalf_ctx* ctx);                // host_config.cpp: the e
             return set_err(ctx, MCALF_ERR_INVALID, "%s: not available on a multi-device context (mcalf_create_multi); " \
                            "use a single-device context per GPU", what);                                          \
     } while (0)
+
+// ---- host_launch.cpp: the batch kernels ---------------------------------------------------------------------------------
+// The kernel arguments of rows [row0, row0 + nrows) of a batch (everything but the launch geometry).
+// wide_stage (contexts whose LSF is wider than a tile, launch_wide): which of the launch's kernels the block is for
+enum { kWideNone = 0, kWideFused = 1, kWideKernels = 2 };
+KArgs make_kargs(const mcalf_ctx* ctx, const LaunchReq& q, int64_t row0, int64_t nrows, int chunk, int wide_stage = kWideNone);
+int launch(mcalf_ctx* ctx, const LaunchReq& q);        // enqueue one batch on q.stream (asynchronous)
+// Rows [row0, row0 + nrows) of the batch on `stream` (a row block has a stream of its own): set-up, fused kernel, finalize when tiled.
+int launch_range(mcalf_ctx* ctx, const LaunchReq& q, int64_t row0, int64_t nrows, int chunk, hipStream_t stream, bool timed_ok,
+                 int wide_stage = kWideNone);
+int launch_preflight(mcalf_ctx* ctx, int mode, int64_t batch);   // what can fail WITHOUT anything having been enqueued
+int launch_finalize(mcalf_ctx* ctx, const KArgs& a, int64_t nrows, int mode, hipStream_t stream, int nparts = 0, bool signal = false);
+int grow_sample_ws(mcalf_ctx* ctx, int64_t batch);     // the per-live-point workspaces of the set-up kernel
+int pick_chunks(const mcalf_ctx* ctx, int64_t batch);
+constexpr int kCopyStream = 1;          // aux[1]: the copy stream of the row-block pipeline; aux[0]: its second compute stream
+int ensure_aux(mcalf_ctx* ctx, int naux, bool pipeline = false);
+// The event pair around a fused launch while a profile is being taken (mcalf_profile_begin) and has room for it.
+int profile_start(mcalf_ctx* ctx, hipStream_t stream, bool* timed);
+int profile_stop(mcalf_ctx* ctx, hipStream_t stream, bool timed);
+
+// ---- host_wide.cpp: an LSF wider than a workgroup tile ------------------------------------------------------------------
+int64_t wide_rows_per_pass(const mcalf_ctx* ctx, int64_t batch);
+int grow_wide_ws(mcalf_ctx* ctx, int64_t rows, bool partials, bool onecomp_rows);   // the scratch of one pass of `rows` live points
+int launch_wide(mcalf_ctx* ctx, const LaunchReq& q);
+
+// ---- host_pipeline.cpp: the row-block pipeline of a large host-pointer batch ----------------------------------------------
+int ensure_stage(mcalf_ctx* ctx, size_t need);         // the page-locked staging block (h_stage) of at least `need` doubles
+int run_host_pipelined(mcalf_ctx* ctx, const HostReq& h);
+void host_trace_report(mcalf_ctx* ctx);                // MCALF_HOST_TRACE, the zero-copy call's and the pipeline's phases
 
 // ---- host_multi.cpp: one process driving several devices ---------------------------------------------------------------
 void multi_release(mcalf_ctx* ctx);                    // stops the workers, destroys the sub-contexts
@@ -354,26 +415,19 @@ int multi_run(mcalf_ctx* ctx, int64_t batch, WorkFn fn, void* arg);      // (fn'
 int stream_probe_xcds(mcalf_ctx* ctx);                 // which XCDs the context's stream reaches (ctx->xcd_mask)
 int stream_prepare(mcalf_ctx* ctx, int mode, int64_t batch);
 int ensure_ctl(mcalf_ctx* ctx);                        // the page-locked words a launch and the host exchange (h_ctl / d_ctl)
-int stream_launch(mcalf_ctx* ctx, int mode, const double* dP, int64_t batch, double* d_out, hipStream_t stream, int wgs,
-                  int64_t eager_rows, bool staged, bool host_rows, bool from_cube = false);
+int stream_launch(mcalf_ctx* ctx, const LaunchReq& q, int wgs, int64_t eager_rows, bool staged, bool host_rows);
 bool stream_qualifies(const mcalf_ctx* ctx, int64_t batch);
 void host_scale_cube(const mcalf_ctx* ctx, const double* cube, int64_t batch, double* theta);
-int run_host_stream(mcalf_ctx* ctx, int mode, const double* P, int64_t batch, int rowlen, double* out_scalar, bool* taken,
-                    bool from_cube = false, double* theta_out = nullptr);
+int run_host_stream(mcalf_ctx* ctx, const HostReq& h, bool* taken);
 void stream_trace_report(mcalf_ctx* ctx);
-void host_trace_report(mcalf_ctx* ctx);          // host_abi.cpp: MCALF_HOST_TRACE, the row-block pipeline's phases
 
 // ---- broker.cpp: resident one-theta evaluator ---------------------------------------------------------------------------
 void resident_stop(mcalf_ctx* ctx);
 bool resident_serves(const mcalf_ctx* ctx, int mode, int64_t batch, int rowlen, bool from_cube);
 int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out);
 
-// ---- host_grad.cpp: the derivative entries ----------------------------------------------------------------------------
-void grad_release(mcalf_ctx* ctx);                     // frees every buffer of ctx->gb
-
 // ---- host_eqw.cpp: the equivalent-width entries -------------------------------------------------------------------------
 int eqw_prepare(mcalf_ctx* ctx, const double* wl);     // mcalf_create: dlam on the device
-void eqw_release(mcalf_ctx* ctx);                      // frees dlam and every buffer of ctx->eb
 
 // ---- comm.cpp -----------------------------------------------------------------------------------------------------------
 void comm_release(mcalf_ctx* ctx);

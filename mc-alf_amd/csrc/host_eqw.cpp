@@ -24,7 +24,7 @@ int64_t eqw_chunk_rows(const mcalf_ctx* ctx) {
     return std::min<int64_t>(kEqwMaxRows, std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row));
 }
 
-int grow_buf(mcalf_ctx* ctx, int b, size_t elems) { return grow(ctx, &ctx->eb[b].p, &ctx->eb[b].cap, elems); }
+int grow_buf(mcalf_ctx* ctx, int b, size_t elems) { return grow(ctx, ctx->eb[b], elems); }
 
 // Everything that is wrong with a call before any device work; `name` is the entry that reports it.
 int eqw_check(mcalf_ctx* ctx, const char* name, const double* P, int64_t batch, int32_t indexing, const double* Wcomp, const double* Wblend) {
@@ -51,7 +51,7 @@ int run_eqw(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, d
         return rc;
     EqwArgs a = {};
     a.nu = ctx->d_nu; a.dlam = ctx->d_dlam; a.lines = ctx->d_lines; a.tabs = ctx->d_tabs;
-    a.recs = ctx->eb[mcalf_ctx::kEbRecs].p; a.part = ctx->eb[mcalf_ctx::kEbPart].p;
+    a.recs = ctx->eb[mcalf_ctx::kEbRecs]; a.part = ctx->eb[mcalf_ctx::kEbPart];
     a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = eqw_ntiles(ctx); a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax;
     a.startind = ctx->startind; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0; a.indexing = indexing;
     const size_t nrec = (size_t)eqw_nrec(ctx), ncells = (size_t)eqw_ncells(ctx);
@@ -80,20 +80,18 @@ int run_host(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t indexing, d
         }, &c);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(P), is_pinned_host(Wcomp ? Wcomp : Wblend));
     const size_t nP = (size_t)batch * ctx->ndim, nC = Wcomp ? (size_t)batch * (size_t)eqw_nrec(ctx) : 0, nB = Wblend ? (size_t)batch * ctx->nlines : 0;
     int rc;
     if ((rc = grow_buf(ctx, mcalf_ctx::kEbP, nP)) || (rc = grow_buf(ctx, mcalf_ctx::kEbWcomp, nC)) || (rc = grow_buf(ctx, mcalf_ctx::kEbWblend, nB))) return rc;
-    const mcalf_ctx::GradBuf* eb = ctx->eb;
+    const DevBuf<double>* eb = ctx->eb;
     double* dC = nC ? eb[mcalf_ctx::kEbWcomp].p : nullptr;
     double* dB = Wblend ? eb[mcalf_ctx::kEbWblend].p : nullptr;
-    HIP_TRY(ctx, hipMemcpyAsync(eb[mcalf_ctx::kEbP].p, P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_eqw(ctx, eb[mcalf_ctx::kEbP].p, batch, indexing, dC, dB, ctx->stream))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(eb[mcalf_ctx::kEbP], P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_eqw(ctx, eb[mcalf_ctx::kEbP], batch, indexing, dC, dB, ctx->stream))) return rc;
     if (nC) HIP_TRY(ctx, hipMemcpyAsync(Wcomp, dC, nC * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (nB) HIP_TRY(ctx, hipMemcpyAsync(Wblend, dB, nB * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->last.path = MCALF_PATH_HOST_STAGED;
-    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
-    ctx->last.pinned_out = is_pinned_host(Wcomp ? Wcomp : Wblend) ? 1 : 0;
     return MCALF_OK;
 }
 
@@ -106,15 +104,9 @@ int eqw_prepare(mcalf_ctx* ctx, const double* wl) {
     std::vector<double> dlam((size_t)ctx->npix);
     for (long i = 1; i < ctx->npix; ++i) dlam[i] = wl[i] - wl[i - 1];
     dlam[0] = dlam[1];
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_dlam, dlam.size() * sizeof(double)));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_dlam.p, dlam.size() * sizeof(double)));
     HIP_TRY(ctx, hipMemcpy(ctx->d_dlam, dlam.data(), dlam.size() * sizeof(double), hipMemcpyHostToDevice));
     return MCALF_OK;
-}
-
-void eqw_release(mcalf_ctx* ctx) {
-    if (ctx->d_dlam) (void)hipFree(ctx->d_dlam);
-    for (mcalf_ctx::GradBuf& b : ctx->eb)
-        if (b.p) (void)hipFree(b.p);
 }
 
 extern "C" int mcalf_eqw_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t indexing, double* Wcomp, double* Wblend) {
@@ -130,6 +122,6 @@ extern "C" int mcalf_eqw_batch_device(mcalf_ctx* ctx, const double* dP, int64_t 
     MCALF_SINGLE_ONLY(ctx, "mcalf_eqw_batch_device");
     if (batch == 0) return MCALF_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    begin_call(ctx, MCALF_PATH_DEVICE, false, false);
     return run_eqw(ctx, dP, batch, indexing, dWcomp, dWblend, (hipStream_t)stream);
 }

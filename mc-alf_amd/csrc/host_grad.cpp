@@ -2,7 +2,7 @@
 // the Hessian-vector product of logL, and mcalf_voigt_hjerting_grad.  A product is a row of the table below -- its
 // workspaces, whether logL comes first, its kernel sequence, its row pointers -- and ONE driver (run_product) runs any of
 // them pass by pass over row blocks whose per-row workspaces stay within kGradChunkBytes.  logL itself comes from the
-// likelihood's own launch (host_abi.cpp: launch), so the entries agree on it bit for bit.  ONE helper serves the
+// likelihood's own launch (host_launch.cpp: launch), so the entries agree on it bit for bit.  ONE helper serves the
 // host-pointer entries (run_host: staging, multi-device split) and one the device-pointer entries (run_device).
 #include <cmath>
 
@@ -32,7 +32,7 @@ int64_t ws_row_elems(const mcalf_ctx* ctx, int b) {
 // Rows per pass of a product whose per-row workspaces are ctx->gb[0, nws): EVERY one of them within kGradChunkBytes -- the
 // taps of a wide-LSF context are thousands of doubles per row -- and at most kGradMaxRows rows: the pixel kernels carry the
 // row on grid.y (a short spectrum's rows are ~2 KB each, so the byte bound alone would allow ~200 000 of them), the same cap
-// as the likelihood's wide path (host_abi.cpp: wide_rows_per_pass).  The HVP's three more workspaces cut its passes smaller.
+// as the likelihood's wide path (host_wide.cpp: wide_rows_per_pass).  The HVP's three more workspaces cut its passes smaller.
 constexpr int64_t kGradMaxRows = 65535;
 int64_t grad_chunk_rows(const mcalf_ctx* ctx, int nws) {
     int64_t per_row = 0;
@@ -40,16 +40,16 @@ int64_t grad_chunk_rows(const mcalf_ctx* ctx, int nws) {
     return std::min<int64_t>(kGradMaxRows, std::max<int64_t>(1, (int64_t)kGradChunkBytes / per_row));
 }
 
-int grow_buf(mcalf_ctx* ctx, int b, size_t elems) { return grow(ctx, &ctx->gb[b].p, &ctx->gb[b].cap, elems); }
+int grow_buf(mcalf_ctx* ctx, int b, size_t elems) { return grow(ctx, ctx->gb[b], elems); }
 
 // What every pass of a batch shares; the row pointers and the row count are set per pass.
 GradArgs grad_args(const mcalf_ctx* ctx) {
     GradArgs a = {};
-    const mcalf_ctx::GradBuf* gb = ctx->gb;
+    const DevBuf<double>* gb = ctx->gb;
     a.nu = ctx->d_nu; a.obj = ctx->d_obj; a.ispec2 = ctx->d_ispec2; a.lgis = ctx->d_lgis; a.lines = ctx->d_lines;
-    a.rows = gb[mcalf_ctx::kGbRows].p; a.recs = gb[mcalf_ctx::kGbRecs].p; a.taps = gb[mcalf_ctx::kGbTaps].p; a.dtaps = gb[mcalf_ctx::kGbDtaps].p;
-    a.F = gb[mcalf_ctx::kGbF].p; a.q = gb[mcalf_ctx::kGbQ].p; a.part = gb[mcalf_ctx::kGbPart].p;
-    a.ddtaps = gb[mcalf_ctx::kGbDdtaps].p; a.hq = gb[mcalf_ctx::kGbHq].p; a.hdq = gb[mcalf_ctx::kGbHdq].p;
+    a.rows = gb[mcalf_ctx::kGbRows]; a.recs = gb[mcalf_ctx::kGbRecs]; a.taps = gb[mcalf_ctx::kGbTaps]; a.dtaps = gb[mcalf_ctx::kGbDtaps];
+    a.F = gb[mcalf_ctx::kGbF]; a.q = gb[mcalf_ctx::kGbQ]; a.part = gb[mcalf_ctx::kGbPart];
+    a.ddtaps = gb[mcalf_ctx::kGbDdtaps]; a.hq = gb[mcalf_ctx::kGbHq]; a.hdq = gb[mcalf_ctx::kGbHdq];
     a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = grad_ntiles(ctx); a.tapcap = grad_tapcap(ctx); a.nslots = grad_nslots(ctx);
     a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax; a.nfill = ctx->nfill; a.startind = ctx->startind; a.endind = ctx->endind;
     a.freespecres = ctx->freespecres; a.freecont = ctx->freecont; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0;
@@ -108,9 +108,10 @@ int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStre
     if (p.logl) {
         if (!c.L) {
             if ((rc = grow_buf(ctx, mcalf_ctx::kGbLogL, (size_t)batch))) return rc;
-            c.L = ctx->gb[mcalf_ctx::kGbLogL].p;
+            c.L = ctx->gb[mcalf_ctx::kGbLogL];
         }
-        if ((rc = launch(ctx, kModeLogL, c.P, batch, 0, 0, c.L, nullptr, stream))) return rc;
+        LaunchReq q(kModeLogL, c.P, batch, stream); q.d_out = c.L;
+        if ((rc = launch(ctx, q))) return rc;
     }
     GradArgs a = grad_args(ctx);
     for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
@@ -130,7 +131,7 @@ int run_device(mcalf_ctx* ctx, const Product& p, const Call& c, int64_t batch, v
         return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
     MCALF_SINGLE_ONLY(ctx, p.device_entry);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->last.path = MCALF_PATH_DEVICE; ctx->last.pinned_in = ctx->last.pinned_out = 0;
+    begin_call(ctx, MCALF_PATH_DEVICE, false, false);
     return run_product(ctx, p, c, batch, (hipStream_t)stream);
 }
 
@@ -151,29 +152,22 @@ int run_host(mcalf_ctx* ctx, const Product& p, const double* P, const double* X,
         }, &c);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(P), is_pinned_host(Y));   // H2D, launch, D2H on the context's stream
     const int bX = p.x_pix ? mcalf_ctx::kGbX : mcalf_ctx::kGbV, bY = p.y_pix ? mcalf_ctx::kGbX : mcalf_ctx::kGbG;
     const size_t nP = (size_t)batch * ctx->ndim, nX = p.has_x ? (size_t)batch * xw : 0, nY = (size_t)batch * yw;
     int rc;
     if ((rc = grow_buf(ctx, mcalf_ctx::kGbP, nP)) || (rc = grow_buf(ctx, bX, nX)) || (rc = grow_buf(ctx, bY, nY))) return rc;
-    const mcalf_ctx::GradBuf* gb = ctx->gb;
-    HIP_TRY(ctx, hipMemcpyAsync(gb[mcalf_ctx::kGbP].p, P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (p.has_x) HIP_TRY(ctx, hipMemcpyAsync(gb[bX].p, X, nX * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_product(ctx, p, {gb[mcalf_ctx::kGbP].p, p.has_x ? gb[bX].p : nullptr, gb[bY].p, nullptr}, batch, ctx->stream))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(Y, gb[bY].p, nY * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (L) HIP_TRY(ctx, hipMemcpyAsync(L, gb[mcalf_ctx::kGbLogL].p, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const DevBuf<double>* gb = ctx->gb;
+    HIP_TRY(ctx, hipMemcpyAsync(gb[mcalf_ctx::kGbP], P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (p.has_x) HIP_TRY(ctx, hipMemcpyAsync(gb[bX], X, nX * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run_product(ctx, p, {gb[mcalf_ctx::kGbP], p.has_x ? gb[bX].p : nullptr, gb[bY], nullptr}, batch, ctx->stream))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(Y, gb[bY], nY * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (L) HIP_TRY(ctx, hipMemcpyAsync(L, gb[mcalf_ctx::kGbLogL], (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->last.path = MCALF_PATH_HOST_STAGED;              // H2D, launch, D2H on the context's stream (set after the launch's own)
-    ctx->last.pinned_in = is_pinned_host(P) ? 1 : 0;
-    ctx->last.pinned_out = is_pinned_host(Y) ? 1 : 0;
     return MCALF_OK;
 }
 
 }  // namespace
-
-void grad_release(mcalf_ctx* ctx) {
-    for (mcalf_ctx::GradBuf& b : ctx->gb)
-        if (b.p) (void)hipFree(b.p);
-}
 
 extern "C" int mcalf_loglike_grad_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, double* dlogL, double* dG,
                                                void* stream) {

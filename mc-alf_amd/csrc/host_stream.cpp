@@ -18,10 +18,8 @@ void stream_trace_report(mcalf_ctx* ctx) {
 // Workspaces of the streaming launch for `batch` live points, and the words it shares with the host.
 int stream_prepare(mcalf_ctx* ctx, int mode, int64_t batch) {
     int rc;
-    const bool reduces = (mode == kModeLogL || mode == kModeChi2);
-    if (reduces && ctx->ntiles > 1 && (rc = grow(ctx, &ctx->d_partial, &ctx->cap_partial, (size_t)batch * ctx->ntiles * 4)))
-        return rc;
-    if ((size_t)batch > ctx->cap_sws) {
+    if (mode_reduces(mode) && ctx->ntiles > 1 && (rc = grow(ctx, ctx->d_partial, (size_t)batch * ctx->ntiles * 4))) return rc;
+    if ((size_t)batch > ctx->sws_rows) {
         // the launch's waves hand these to each other while it runs, through system-scope accesses (see the streaming
         // helpers); ordinary device memory
         // (every live point's records, taps and header start on a 128-byte line of their own)
@@ -32,17 +30,17 @@ int stream_prepare(mcalf_ctx* ctx, int mode, int64_t batch) {
         const size_t npar = ((size_t)batch * ctx->ndim + 15) & ~(size_t)15;
         const size_t bytes = (nrec + ntap + nhdr + npar) * sizeof(double) + (size_t)batch * sizeof(unsigned int) + 256;
         if (ctx->d_sws) HIP_TRY(ctx, hipFree(ctx->d_sws));
-        ctx->d_sws = nullptr; ctx->cap_sws = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_sws, bytes));
+        ctx->d_sws.p = nullptr; ctx->sws_rows = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_sws.p, bytes));
         HIP_TRY(ctx, hipMemset(ctx->d_sws, 0, bytes));                                      // (stamps start at 1, queues at 0)
         HIP_TRY(ctx, hipDeviceSynchronize());            // (the fill may still be running, and the launch streams do not wait for the null stream)
-        ctx->s_recs = static_cast<double*>(ctx->d_sws);
+        ctx->s_recs = static_cast<double*>(ctx->d_sws.p);
         ctx->s_taps = ctx->s_recs + nrec;
         ctx->s_hdr = reinterpret_cast<SampleHdr*>(ctx->s_taps + ntap);
         ctx->s_P = ctx->s_taps + ntap + nhdr;
         ctx->d_ready = reinterpret_cast<unsigned int*>(ctx->s_P + npar);
         ctx->d_sctl = reinterpret_cast<StreamCtl*>((reinterpret_cast<uintptr_t>(ctx->d_ready + batch) + 63) & ~(uintptr_t)63);
-        ctx->cap_sws = (size_t)batch;
+        ctx->sws_rows = (size_t)batch;
         // (the generation count goes on: the new stamps are zero and no launch is ever stamped 0, while a count that
         // restarted could equal the completion word an earlier launch left in h_ctl[1])
     }
@@ -52,23 +50,24 @@ int stream_prepare(mcalf_ctx* ctx, int mode, int64_t batch) {
 // The page-locked, device-mapped words a launch and the host exchange (h_ctl: see host_ctx.h).
 int ensure_ctl(mcalf_ctx* ctx) {
     if (!ctx->h_ctl) {
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_ctl, kCtlWords * sizeof(unsigned int), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset((void*)ctx->h_ctl, 0, kCtlWords * sizeof(unsigned int));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->d_ctl, (void*)ctx->h_ctl, 0));
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_ctl.p, kCtlWords * sizeof(unsigned int), hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset((void*)ctx->h_ctl.p, 0, kCtlWords * sizeof(unsigned int));
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->d_ctl, (void*)ctx->h_ctl.p, 0));
     }
     return MCALF_OK;
 }
 
-// Enqueue ONE streaming launch over `batch` live points (and the finalize kernel of a tiled spectrum) on `stream`.
-// dP: the parameter rows as the DEVICE addresses them (HBM, or page-locked host memory); wgs: workgroups dedicated to
+// Enqueue ONE streaming launch over the live points of `q` (and the finalize kernel of a tiled spectrum) on its stream.
+// q.dP: the parameter rows as the DEVICE addresses them (HBM, or page-locked host memory); wgs: workgroups dedicated to
 // the set-up while rows are outstanding (a multiple of the XCD count: so many per XCD); eager_rows: blocks of eight
 // rows PER XCD that any of its workgroups may set up; staged: the kernel waits for the host's row count
 // (ctx->h_ctl[kCtlArrived]).
-int stream_launch(mcalf_ctx* ctx, int mode, const double* dP, int64_t batch, double* d_out, hipStream_t stream, int wgs,
-                  int64_t eager_rows, bool staged, bool host_rows, bool from_cube) {
+int stream_launch(mcalf_ctx* ctx, const LaunchReq& q, int wgs, int64_t eager_rows, bool staged, bool host_rows) {
+    const int64_t batch = q.batch; const hipStream_t stream = q.stream;
+    int rc;
     // (from_cube: the rows are unit-cube rows, mapped through the prior box while they are decoded; the transformed rows
     // themselves, when the caller wants them, are formed on the host while the launch runs: host_scale_cube)
-    KArgs a = make_kargs(ctx, mode, dP, 0, batch, 0, 0, 0, d_out, nullptr, from_cube, nullptr);
+    KArgs a = make_kargs(ctx, q, 0, batch, 0);
     a.taps_shared = 0;                                    // (a row's stamp covers its own taps only)
     a.recs = ctx->s_recs; a.taps = ctx->s_taps; a.hdr = ctx->s_hdr;
     a.persist = 1;
@@ -76,7 +75,7 @@ int stream_launch(mcalf_ctx* ctx, int mode, const double* dP, int64_t batch, dou
     const int grid = 2 * ctx->num_cu;
     if (++ctx->stream_gen == 0u) {                        // stamps wrapped: none of the old ones may match again
         HIP_TRY(ctx, hipStreamSynchronize(stream));
-        HIP_TRY(ctx, hipMemset(ctx->d_ready, 0, ctx->cap_sws * sizeof(unsigned int)));
+        HIP_TRY(ctx, hipMemset(ctx->d_ready, 0, ctx->sws_rows * sizeof(unsigned int)));
         HIP_TRY(ctx, hipDeviceSynchronize());
         ctx->stream_gen = 1u;
     }
@@ -98,19 +97,16 @@ int stream_launch(mcalf_ctx* ctx, int mode, const double* dP, int64_t batch, dou
     ctx->last.persistent = 1; ctx->last.grid = grid; ctx->last.items = a.nitems; ctx->last.lines_per_sync = ctx->lps;
     ctx->last.selfhalo = ctx->selfhalo; ctx->last.ordered = 0; ctx->last.inline_setup = 0;
     ctx->last.stream_setup_wgs = wgs;
-    const bool timed = ctx->profiling && ctx->ev_used + 2 <= ctx->ev.size();
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[ctx->ev_used], stream));
+    bool timed = false;
+    if ((rc = profile_start(ctx, stream, &timed))) return rc;
     {
         void* kargs[] = {(void*)&a};
         HIP_TRY(ctx, hipLaunchKernel(fused_kernel_ptr(ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX, ctx->selfhalo != 0, ctx->lps, false, true),
                                      dim3((unsigned)grid), dim3(kBlock), kargs, ctx->lds_bytes, stream));
     }
-    if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[ctx->ev_used + 1], stream));
-        ctx->ev_used += 2;
-    }
+    if ((rc = profile_stop(ctx, stream, timed))) return rc;
     // (tiled spectra: the finalize kernel writes the results; when they go to page-locked host memory it also tells the host)
-    if ((mode == kModeLogL || mode == kModeChi2) && ctx->ntiles > 1) return launch_finalize(ctx, a, batch, mode, stream, 0, host_rows);
+    if (q.reduces() && ctx->ntiles > 1) return launch_finalize(ctx, a, batch, q.mode, stream, 0, host_rows);
     return MCALF_OK;
 }
 
@@ -202,13 +198,13 @@ void host_scale_cube(const mcalf_ctx* ctx, const double* cube, int64_t batch, do
 // stalled for longer than MCALF_STREAM_TIMEOUT) fails over to the pipeline too, after the grid has drained.
 // On any device shape but the eight XCDs of an unpartitioned MI355X the call does not qualify either (stream_probe_xcds), and
 // a launch whose kernel reports an XCD without workgroups is discarded like one that timed out.
-int run_host_stream(mcalf_ctx* ctx, int mode, const double* P, int64_t batch, int rowlen, double* out_scalar, bool* taken,
-                    bool from_cube, double* theta_out) {
+int run_host_stream(mcalf_ctx* ctx, const HostReq& h, bool* taken) {
+    const double* P = h.P; double* out_scalar = h.out_scalar;
+    const int64_t batch = h.batch; const int rowlen = h.rowlen;
     *taken = false;
     const bool trace = ctx->stream_trace;
     double tm[7] = {};
     if (trace) tm[0] = now_us();
-    ctx->last.stream_fallback = 0; ctx->last.stream_wgs_min = ctx->last.stream_wgs_max = 0;
     if (!ctx->stream_on || ctx->chunks_req > 0 || ctx->host_plan_n > 0 || ctx->profiling || !stream_qualifies(ctx, batch)) return MCALF_OK;
     // Tiled spectra (automatic): the streaming launch up to kStreamTiledMaxItems work items, the row-block pipeline beyond.
     // Measured on MI355X, config E (5 tiles per live point), pageable rows, host step over the device-resident one:
@@ -234,15 +230,8 @@ int run_host_stream(mcalf_ctx* ctx, int mode, const double* P, int64_t batch, in
     }
     int rc;
     if (trace) tm[1] = now_us();
-    if ((rc = stream_prepare(ctx, mode, batch))) return rc;
-    const size_t need = (pin_in ? 0 : (size_t)batch * rowlen) + (pin_out ? 0 : (size_t)batch);
-    if (need > ctx->cap_stage) {
-        if (ctx->h_stage) HIP_TRY(ctx, hipHostFree(ctx->h_stage));
-        ctx->h_stage = nullptr; ctx->cap_stage = 0;
-        // coherent: the kernel reads rows of this block while the host is still writing later ones
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_stage, need * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        ctx->cap_stage = need;
-    }
+    if ((rc = stream_prepare(ctx, h.mode, batch))) return rc;
+    if ((rc = ensure_stage(ctx, (pin_in ? 0 : (size_t)batch * rowlen) + (pin_out ? 0 : (size_t)batch)))) return rc;
     double* stage_in = pin_in ? nullptr : ctx->h_stage;
     double* stage_out = pin_out ? out_scalar : ctx->h_stage + (pin_in ? 0 : (size_t)batch * rowlen);
     if (!pin_in) HIP_TRY(ctx, hipHostGetDevicePointer((void**)&dP_view, stage_in, 0));
@@ -254,15 +243,15 @@ int run_host_stream(mcalf_ctx* ctx, int mode, const double* P, int64_t batch, in
     ctx->h_ctl[0] = 0u;
     ctx->h_ctl[kCtlArrived] = 0u;
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    ctx->last.path = MCALF_PATH_HOST_STREAM; ctx->last.row_blocks = 1;
-    ctx->last.pinned_in = pin_in ? 1 : 0; ctx->last.pinned_out = pin_out ? 1 : 0;
+    set_path(ctx, MCALF_PATH_HOST_STREAM, pin_in, pin_out); ctx->last.row_blocks = 1;
     if (trace) tm[2] = now_us();
     // the rows an XCD's first items need are set up by whichever of its workgroups gets there first, the rest by its
     // dedicated workgroups
     const int64_t eager_blocks = ctx->stream_eager > 0 ? ctx->stream_eager : (first_rows + 7) / 8;
-    if ((rc = stream_launch(ctx, mode, dP_view, batch, d_out_view, ctx->stream, wgs, eager_blocks, !pin_in, true, from_cube)))
-        return rc;
-    const bool tiled = (mode == kModeLogL || mode == kModeChi2) && ctx->ntiles > 1;
+    LaunchReq q = h.on_device(dP_view, ctx->stream);
+    q.d_out = d_out_view;
+    if ((rc = stream_launch(ctx, q, wgs, eager_blocks, !pin_in, true))) return rc;
+    const bool tiled = h.reduces() && ctx->ntiles > 1;
     if (trace) tm[3] = now_us();
     // The kernel is in flight (or about to be): stage the rows.  Nothing below can fail before every row has been
     // published, so the grid never waits for a row that is not coming.
@@ -274,7 +263,7 @@ int run_host_stream(mcalf_ctx* ctx, int mode, const double* P, int64_t batch, in
             __atomic_store_n(const_cast<unsigned int*>(ctx->h_ctl + kCtlArrived), (unsigned int)(r0 + n), __ATOMIC_RELEASE);
         }
     }
-    if (theta_out) host_scale_cube(ctx, P, batch, theta_out);   // (under the launch)
+    if (h.theta_out) host_scale_cube(ctx, P, batch, h.theta_out);   // (under the launch)
     hipError_t he = hipGetLastError();
     if (trace) tm[4] = now_us();
     // Completion: the word the last workgroup writes once every result has been acknowledged (a stream wait costs an

@@ -105,3 +105,14 @@ def require_streaming_shape(fit):
     mask = fit.last_launch().xcd_mask
     if mask != 0xFF:
         pytest.skip(f"this device's stream reaches XCDs {mask:#x}, not 0xff: the streaming launch is not taken here")
+
+
+def tiny_problem(npix, seed=0):
+    """One line, one component on a logarithmic grid of `npix` pixels at 2 km/s per pixel, fixed resolution and continuum
+    (ndim 4): the smallest problem that still goes through every kernel -- one pixel tile up to ~4000 pixels, two beyond."""
+    rng = np.random.default_rng(seed)
+    wl = 6190.0 * np.exp(np.arange(npix) * 2.0 / 2.99792458e5)
+    z0 = wl[npix // 2] / 1548.204 - 1.0
+    return dict(fitrange=[[wl[0] - 0.01, wl[-1] + 0.01]], fitlines=["CIV 1548"], linepars=[(1548.204, 0.1899, 2.643e8)], ncomp=[1, 1],
+                nfill=0, specres=[8.0], contval=[1.0], Nrange=[12.0, 14.5], brange=[5.0, 40.0], zrange=[z0 - 2e-4, z0 + 2e-4],
+                spectrum=(wl, 1 + rng.normal(0, 0.03, npix), rng.uniform(0.01, 0.05, npix)), velstep=2.0)

@@ -8,7 +8,7 @@ import torch
 
 import mcalf_amd
 from mcalf_amd import _lib, workloads
-from cases import oracle_synth, require_streaming_shape
+from cases import oracle_synth, require_streaming_shape, tiny_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -140,13 +140,47 @@ def test_cube_host_entry_takes_the_fast_paths_of_the_theta_entry(cfg, n, path):
             ll = fit.last_launch()
             assert ll.path == {"stream": _lib.MCALF_PATH_HOST_STREAM, "small": _lib.MCALF_PATH_HOST_ZEROCOPY,
                                "staged": _lib.MCALF_PATH_HOST_STAGED}[path]
-            if path != "staged":
-                assert ll.stream_polled == 1
+            assert ll.stream_polled == (0 if path == "staged" else 1)
             want_theta = (np.array([fit._scale_cube_pc(c.copy()) for c in cubes]) if int_ncomp else
                           np.array([fit._scale_cube_mn(c.copy(), fit.ndim, fit.ndim) for c in cubes]))
             assert np.array_equal(theta, want_theta)
             assert np.array_equal(logL, fit.loglike_batch(np.array([fit._scale_cube_pc(c.copy()) for c in cubes])))
             assert np.array_equal(fit.loglike_cube_batch(cubes, int_ncomp=int_ncomp, return_theta=False), logL)
+
+
+def test_the_launch_record_belongs_to_the_last_call():
+    """`mcalf_last_launch` describes the LAST call and nothing of an earlier one: after a zero-copy call (completion read off
+    the results: stream_polled 1) -- and, where the device streams, after a streaming launch (dedicated set-up workgroups,
+    workgroup counts per XCD) -- a staged model call and a device-entry call on the same context report their own path
+    with every streaming and page-locked field 0."""
+    kw = tiny_problem(200)
+    P = workloads.draw_P(kw, 2048, np.random.default_rng(5))
+    zero = ("stream_polled", "stream_setup_wgs", "stream_fallback", "stream_wgs_min", "stream_wgs_max", "pinned_in", "pinned_out")
+    with mcalf_amd.als_fitter(None, **kw) as fit:
+        assert fit.info.ntiles == 1
+        firsts = [(3, _lib.MCALF_PATH_HOST_ZEROCOPY)]
+        if fit.last_launch().xcd_mask == 0xFF:              # (what require_streaming_shape asks for)
+            firsts.append((2048, _lib.MCALF_PATH_HOST_STREAM))
+        dP = torch.from_numpy(P[:3]).cuda()
+        out = torch.empty(3, dtype=torch.float64, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for n, path in firsts:
+            for then in ("model", "device"):
+                fit.loglike_batch(P[:n])
+                ll = fit.last_launch()
+                assert (ll.path, ll.stream_polled) == (path, 1)
+                if path == _lib.MCALF_PATH_HOST_STREAM:
+                    assert ll.stream_setup_wgs > 0 and ll.stream_wgs_min > 0 and ll.stream_wgs_max > 0
+                if then == "model":
+                    fit.model_batch(P[:3])
+                    want = _lib.MCALF_PATH_HOST_STAGED
+                else:
+                    _lib.check(fit._lib.mcalf_loglike_batch_device(fit._ctx, dP.data_ptr(), 3, out.data_ptr(), st), fit._ctx)
+                    torch.cuda.synchronize()
+                    want = _lib.MCALF_PATH_DEVICE
+                ll = fit.last_launch()
+                assert ll.path == want, (n, then)
+                assert {f: getattr(ll, f) for f in zero} == dict.fromkeys(zero, 0), (n, then)
 
 
 def test_cube_entry_requires_a_prior():

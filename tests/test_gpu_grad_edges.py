@@ -139,7 +139,7 @@ def _short_problem():
 def test_more_rows_than_one_grid_y():
     """70 000 rows of a 64-pixel problem in one call.  The pixel kernels carry the row on grid.y, which the device limits
     to 65 536 (hipDeviceAttributeMaxGridDimY on an MI355X), and the byte bound of a pass allows ~200 000 such rows:
-    grad_chunk_rows() caps a pass at 65 535 rows, as the likelihood's wide path caps its own (host_abi.cpp).
+    grad_chunk_rows() caps a pass at 65 535 rows, as the likelihood's wide path caps its own (host_wide.cpp).
     The call returns 0 (the wrapper raises otherwise), every row has the bits it has in a block of 4096, and 64 sampled
     rows -- both sides of the pass boundary among them -- match the reference."""
     kw = _short_problem()

@@ -11,7 +11,9 @@ import torch
 
 import mcalf_amd
 from mcalf_amd import _lib, workloads
-from cases import oracle_synth, problem_from_kwargs, require_streaming_shape
+import functools
+
+from cases import oracle_synth, problem_from_kwargs, require_streaming_shape, tiny_problem
 from oracle import c_oracle
 from oracle import numpy_oracle as o
 
@@ -225,6 +227,80 @@ def test_pipelined_host_entry_is_the_path_taken_and_is_bit_equal(monkeypatch):
         assert fit.last_launch().path == _lib.MCALF_PATH_HOST_PIPELINED
         fit.set_chunks(1)
         assert np.array_equal(fit.loglike_batch(PE), a)
+
+
+@functools.lru_cache(maxsize=None)
+def _two_tile_reference():
+    """The rows of test_one_context_through_every_host_plan_growing and what a FRESH context's device entries give for them
+    (computed once, read only): logL of the theta rows and of the prior-transformed cube rows, chi2, five model rows."""
+    kw = tiny_problem(5000)
+    rng = np.random.default_rng(41)
+    n3 = 65536 // 4 + 8                                   # ndim 4: the first batch beyond 65536 parameters
+    n8 = 2 * n3 + 1
+    P = workloads.draw_P(kw, n8, rng)
+    cubes = rng.random((n3, 4))
+    with mcalf_amd.als_fitter(None, **kw) as ref:
+        assert (ref.info.ntiles, ref.ndim) == (2, 4)
+        theta = cubes * (ref._hi - ref._lo)
+        theta += ref._lo                                  # (separately rounded multiply and add: _scale_cube_pc)
+        theta[:, ref.startind] = np.trunc(theta[:, ref.startind])
+        logl = _device_logl(ref, torch.from_numpy(P).cuda(), n8)
+        cube_logl = _device_logl(ref, torch.from_numpy(theta).cuda(), n3)
+        dm = torch.empty((5, 5000), dtype=torch.float64, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(ref._lib.mcalf_model_batch_device(ref._ctx, torch.from_numpy(P[:5]).cuda().data_ptr(), 5, 0, dm.data_ptr(), st), ref._ctx)
+        torch.cuda.synchronize()
+        res = dict(kw=kw, n3=n3, n8=n8, P=P, cubes=cubes, theta=theta, logl=logl, cube_logl=cube_logl, model=dm.cpu().numpy(),
+                   chi2=ref.chi2_batch(P[:5]))
+    for v in res.values():
+        if isinstance(v, np.ndarray):
+            v.flags.writeable = False
+    return res
+
+
+@pytest.mark.parametrize("stream", ["0", None])
+def test_one_context_through_every_host_plan_growing(stream, monkeypatch):
+    """ONE context of a two-tile spectrum (partials and the finalize kernel in play) through every plan of the host-pointer
+    entries, its buffers growing on the way: 3 rows (zero-copy), 2100 rows (small in bytes: the streaming launch where the
+    device streams and the context allows it), the first batch beyond 65536 parameters through the row-block pipeline,
+    chi2, model rows (staged), a reserve() of a smaller batch, the cube entry small and large, a pipelined batch twice as
+    large.  Every logL has the bits of the device entry on the same rows on a fresh context, the model rows those of
+    mcalf_model_batch_device.  stream "0": the context is created under MCALF_STREAM=0 (read once, at creation), where
+    the pipeline is the default plan of a large call; None: the default environment, the pipeline selected by an explicit
+    block count for its two steps."""
+    r = _two_tile_reference()
+    P, n3, n8 = r["P"], r["n3"], r["n8"]
+    if stream is not None:
+        monkeypatch.setenv("MCALF_STREAM", stream)
+    PIPE, ZERO, STAGED, STREAM = (_lib.MCALF_PATH_HOST_PIPELINED, _lib.MCALF_PATH_HOST_ZEROCOPY, _lib.MCALF_PATH_HOST_STAGED,
+                                  _lib.MCALF_PATH_HOST_STREAM)
+    with mcalf_amd.als_fitter(None, **r["kw"]) as fit:
+        streams = stream is None and fit.last_launch().xcd_mask == 0xFF
+
+        def pipelined(n):
+            if stream is None:
+                fit.set_chunks(2)
+            got = fit.loglike_batch(P[:n])
+            assert fit.last_launch().path == PIPE, n
+            fit.set_chunks(0)
+            return got
+
+        assert np.array_equal(fit.loglike_batch(P[:3]), r["logl"][:3])
+        assert fit.last_launch().path == ZERO
+        assert np.array_equal(fit.loglike_batch(P[:2100]), r["logl"][:2100])
+        assert fit.last_launch().path == (STREAM if streams else ZERO)
+        assert n3 * 4 > 65536
+        assert np.array_equal(pipelined(n3), r["logl"][:n3])
+        assert np.array_equal(fit.chi2_batch(P[:5]), r["chi2"])
+        assert np.array_equal(fit.model_batch(P[:5]), r["model"])
+        assert fit.last_launch().path == STAGED
+        _lib.check(fit._lib.mcalf_reserve(fit._ctx, 64), fit._ctx)
+        for n, path in ((5, ZERO), (n3, STREAM if streams else STAGED)):
+            theta, logl = fit.loglike_cube_batch(r["cubes"][:n])
+            assert fit.last_launch().path == path, n
+            assert np.array_equal(theta, r["theta"][:n]) and np.array_equal(logl, r["cube_logl"][:n]), n
+        assert np.array_equal(pipelined(n8), r["logl"])
+        assert np.array_equal(fit.loglike_batch(P[:3]), r["logl"][:3])
 
 
 @pytest.mark.parametrize("cfg,conv,n", [("C", "numpy", 4096), ("C", "jax", 2300), ("E", "numpy", 1400), ("B", "numpy", 2700)])

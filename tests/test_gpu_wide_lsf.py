@@ -1,7 +1,7 @@
 """GPU: an LSF wider than a workgroup tile.  The fused kernel convolves inside a 4096-pixel LDS tile, halo included; the
 reference simply builds a longer kernel (hires_fitter.py:458-464, astropy `convolve(..., boundary='wrap')`).  Round 5:
 such a context is no longer refused (MCALF_ERR_RANGE) -- the fused kernel runs without convolution and continuum, and two
-more kernels form every live point's taps and convolve periodically (host_abi.cpp: launch_wide; round 6: flux window
+more kernels form every live point's taps and convolve periodically (host_wide.cpp: launch_wide; round 6: flux window
 and taps staged through LDS, taps accumulated -- and `bot` formed -- in tap order as in the fused kernel, so the suite's
 usual bars hold here too) -- same entry points, same conventions.  Checked against the numpy oracle: kernels several times longer than the spectrum (the window
 wraps round it more than once), free resolution and continuum, fillers, logL / chi2 / model / single components / unit-cube
@@ -103,6 +103,27 @@ def test_large_unit_cube_batch_on_a_wide_context_does_not_take_the_streaming_lau
         idx = [0, 1000, 6143]
         want = o.loglike_batch(prob, theta[idx])
         assert np.all(np.abs(ll[idx] - want) < 1e-10 * np.abs(want) + 1e-9)
+
+
+def test_wide_scratch_grows_the_same_way_from_reserve_and_from_a_launch():
+    """mcalf_reserve and the launch share one growth of the wide scratch: reserve 8, evaluate 8 (nothing to grow), evaluate
+    20 (every buffer regrows) on one context of the smallest geometry above -- logL with the bits of the device entry on
+    a fresh context."""
+    kw = _problem(333, 0.0031, (6.0, 9.0), (0.9, 1.1), 2, seed=333)
+    P = workloads.draw_P(kw, 20, np.random.default_rng(11))
+    with mcalf_amd.als_fitter(None, **kw) as ref:
+        assert 2 * ref.info.n_cap + 64 > 4096
+        out = torch.full((20,), float("nan"), dtype=torch.float64, device="cuda")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(ref._lib.mcalf_loglike_batch_device(ref._ctx, torch.from_numpy(P).cuda().data_ptr(), 20, out.data_ptr(), st), ref._ctx)
+        torch.cuda.synchronize()
+        want = out.cpu().numpy()
+    assert np.isfinite(want).any()
+    with mcalf_amd.als_fitter(None, **kw) as fit:
+        _lib.check(fit._lib.mcalf_reserve(fit._ctx, 8), fit._ctx)
+        assert np.array_equal(fit.loglike_batch(P[:8]), want[:8])
+        assert np.array_equal(fit.loglike_batch(P), want)
+        assert np.array_equal(fit.chi2_batch(P[:8]), fit.chi2_batch(P)[:8])
 
 
 def test_wide_lsf_resolution_beyond_the_provisioned_maximum_and_no_convolution():

@@ -1,41 +1,131 @@
 #!/usr/bin/env python3
-"""A/B of two builds of the library: logL of the first N rows of configs C and E through the device entry, each build in
-a process of its own (MCALF_HIP_LIB), compared bit for bit.   python tools/explore/ab_bits.py libA.so libB.so"""
+"""A/B of two builds of the library: every plan of the likelihood's entries once, each case in a FRESH context, each build in a
+process of its own (MCALF_HIP_LIB); outputs compared bit for bit and the whole mcalf_last_launch record field by field.
+
+    python tools/explore/ab_bits.py libA.so libB.so      # exit status 1 when anything differs
+    python tools/explore/ab_bits.py --child out.json     # the cases alone, with the library MCALF_HIP_LIB names (e.g. under a profiler)
+
+Cases: the device entry (one block, three blocks), the zero-copy small call, the streaming launch, the row-block pipeline
+(MCALF_STREAM=0), chi2, model and single-component output, the cube entry (small, streaming, staged), a wide-LSF context,
+single-tile (C, B) and tiled (E) spectra."""
 import json
 import os
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-CHILD = r'''
-import json, os, sys, ctypes as C
-import numpy as np, torch
-sys.path[:0] = [%(root)r, os.path.join(%(root)r, "tests")]
-import mcalf_amd
-from mcalf_amd import _lib, workloads
-from cases import oracle_synth
-res = {}
-for cfg, n in (("C", 4096), ("E", 1024), ("B", 1024)):
-    kw, _, seed = workloads.config(cfg, oracle_synth)
-    P = workloads.draw_P(kw, n, np.random.default_rng(seed), damped=2 if cfg == "E" else 0)
-    with mcalf_amd.als_fitter(None, **kw) as fit:
-        dP = torch.from_numpy(P).cuda(); out = torch.empty(n, dtype=torch.float64, device="cuda")
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(fit._lib.mcalf_loglike_batch_device(fit._ctx, dP.data_ptr(), n, out.data_ptr(), st), fit._ctx)
-        torch.cuda.synchronize()
-        small = fit.loglike_batch(P[:7])               # the one-launch variant
-        host = fit.loglike_batch(P)                    # streaming launch / pipeline
-        res[cfg] = {"dev": out.cpu().numpy().view(np.uint64).tolist(), "small": small.view(np.uint64).tolist(), "host": host.view(np.uint64).tolist()}
-json.dump(res, open(sys.argv[1], "w"))
-'''
-outs = []
-for k, lib in enumerate(sys.argv[1:3]):
-    path = "/tmp/ab_bits_%d.json" % k
-    env = dict(os.environ, MCALF_HIP_LIB=os.path.abspath(lib))
-    subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}, path], env=env, check=True)
-    outs.append(json.load(open(path)))
-for cfg in outs[0]:
-    for key in outs[0][cfg]:
-        a, b = outs[0][cfg][key], outs[1][cfg][key]
-        print(cfg, key, "rows", len(a), "bit-equal" if a == b else "DIFFERENT in %d rows" % sum(x != y for x, y in zip(a, b)))
-    print(cfg, "within build A: host == dev", outs[0][cfg]["host"] == outs[0][cfg]["dev"], "; build B:", outs[1][cfg]["host"] == outs[1][cfg]["dev"])
+
+
+def child(path):
+    import ctypes as C
+    import numpy as np
+    import torch
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import mcalf_amd
+    from mcalf_amd import _lib, workloads
+    from cases import oracle_synth
+    res = {}
+
+    def bits(a):
+        return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64).ravel().tolist()
+
+    def record(fit):
+        ll = fit.last_launch()
+        return {f: int(getattr(ll, f)) for f, _ in ll._fields_}
+
+    def case(name, kw, fn, env=None):
+        """fn(fit) -> arrays, on a fresh context created under `env`."""
+        for k, v in (env or {}).items():
+            os.environ[k] = v
+        try:
+            with mcalf_amd.als_fitter(None, **kw) as fit:
+                out = fn(fit)
+                res[name] = {"out": [bits(a) for a in out], "last": record(fit)}
+        finally:
+            for k in env or {}:
+                del os.environ[k]
+
+    def device(P, chunks=0):
+        def run(fit):
+            n = P.shape[0]
+            fit.set_chunks(chunks)
+            dP = torch.from_numpy(P).cuda()
+            out = torch.empty(n, dtype=torch.float64, device="cuda")
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(fit._lib.mcalf_loglike_batch_device(fit._ctx, dP.data_ptr(), n, out.data_ptr(), st), fit._ctx)
+            torch.cuda.synchronize()
+            return [out.cpu().numpy()]
+        return run
+
+    def onecomp(fit):
+        s = fit.startind
+        z = 0.5 * float(fit._lo[s + 2] + fit._hi[s + 2])
+        return [fit.reconstruct_onecomp(7.5, 0.95, 13.2 + 0.1 * k, z, 12.0 + k) for k in range(3)]
+
+    for cfg, n in (("C", 4096), ("E", 1024), ("B", 1024)):
+        kw, _, seed = workloads.config(cfg, oracle_synth)
+        rng = np.random.default_rng(seed)
+        P = workloads.draw_P(kw, n, rng, damped=2 if cfg == "E" else 0)
+        cubes = rng.random((n, P.shape[1]))
+        case(cfg + " dev", kw, device(P))
+        case(cfg + " dev chunks 3", kw, device(P, 3))
+        case(cfg + " small", kw, lambda fit: [fit.loglike_batch(P[:7])])              # the one-launch variant
+        case(cfg + " host", kw, lambda fit: [fit.loglike_batch(P)])                   # streaming launch (zero-copy where it does not qualify)
+        case(cfg + " chi2", kw, lambda fit: [fit.chi2_batch(P)])
+        case(cfg + " model", kw, lambda fit: [fit.model_batch(P[:5]), fit.model_batch(P[:5], targonly=True)])
+        case(cfg + " onecomp", kw, onecomp)
+        case(cfg + " cube small", kw, lambda fit: list(fit.loglike_cube_batch(cubes[:700])))
+        case(cfg + " cube", kw, lambda fit: list(fit.loglike_cube_batch(cubes)))
+    for cfg, n in (("C", 2600), ("E", 1400), ("E", 13200)):                             # beyond 65536 parameters
+        kw, _, seed = workloads.config(cfg, oracle_synth)
+        rng = np.random.default_rng(seed + 1)
+        P = workloads.draw_P(kw, n, rng, damped=2 if cfg == "E" else 0)
+        cubes = rng.random((n, P.shape[1]))
+        tag = "%s %d" % (cfg, n)
+        case(tag + " host", kw, lambda fit: [fit.loglike_batch(P)])
+        case(tag + " pipelined", kw, lambda fit: [fit.loglike_batch(P)], env={"MCALF_STREAM": "0"})
+        case(tag + " cube", kw, lambda fit: list(fit.loglike_cube_batch(cubes)))            # E 13200: staged
+        case(tag + " cube, no stream", kw, lambda fit: list(fit.loglike_cube_batch(cubes)), env={"MCALF_STREAM": "0"})
+    # a wide-LSF context: the smallest geometry of tests/test_gpu_wide_lsf.py
+    rng = np.random.default_rng(333)
+    wl = np.linspace(6180.0, 6220.0, 335)[1:-1]
+    kw = dict(fitrange=[[6180.0, 6220.0]], fitlines=["CIV 1548", "CIV 1550"], linepars=[(1548.204, 0.1899, 2.643e8), (1550.781, 0.09475, 2.628e8)],
+              ncomp=[1, 3], nfill=2, specres=[6.0, 9.0], contval=[0.9, 1.1], Nrange=[12.0, 14.5], brange=[5.0, 40.0], zrange=[2.995, 3.012],
+              spectrum=(wl, 1 + rng.normal(0, 0.03, 333), rng.uniform(0.01, 0.05, 333)), velstep=0.0031)
+    P = workloads.draw_P(kw, 20, rng)
+    cubes = rng.random((20, P.shape[1]))
+    case("wide dev", kw, device(P))
+    case("wide host", kw, lambda fit: [fit.loglike_batch(P), fit.chi2_batch(P)])
+    case("wide model", kw, lambda fit: [fit.model_batch(P[:3])])
+    case("wide onecomp", kw, lambda fit: [fit.reconstruct_onecomp(8.0, 0.95, 13.5, 3.0, 20.0)])
+    case("wide cube", kw, lambda fit: list(fit.loglike_cube_batch(cubes)))
+    json.dump(res, open(path, "w"))
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "--child":
+        child(sys.argv[2])
+        sys.exit(0)
+    outs = []
+    for k, lib in enumerate(sys.argv[1:3]):
+        path = "/tmp/ab_bits_%d.json" % k
+        env = dict(os.environ, MCALF_HIP_LIB=os.path.abspath(lib))
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, check=True)
+        outs.append(json.load(open(path)))
+    bad = 0
+    assert outs[0].keys() == outs[1].keys()
+    for name in outs[0]:
+        a, b = outs[0][name], outs[1][name]
+        rows = sum(len(x) for x in a["out"])
+        diff = sum(x != y for u, v in zip(a["out"], b["out"]) for x, y in zip(u, v)) + sum(len(u) != len(v) for u, v in zip(a["out"], b["out"]))
+        fields = [f for f in a["last"] if a["last"][f] != b["last"][f]]
+        bad += bool(diff) + bool(fields)
+        print("%-24s %7d values %s; record %s; path %d blocks %d grid %d items %d" % (
+            name, rows, "bit-equal" if not diff else "DIFFERENT in %d" % diff,
+            "equal" if not fields else "DIFFERENT in %s (%s)" % (fields, [(a["last"][f], b["last"][f]) for f in fields]),
+            a["last"]["path"], a["last"]["row_blocks"], a["last"]["grid"], a["last"]["items"]))
+    for cfg in ("C", "E", "B"):
+        print(cfg, "within build A: host == dev", outs[0][cfg + " host"]["out"] == outs[0][cfg + " dev"]["out"],
+              "; build B:", outs[1][cfg + " host"]["out"] == outs[1][cfg + " dev"]["out"])
+    print("RESULT:", "every output bit-equal, every record equal" if not bad else "%d cases differ" % bad)
+    sys.exit(1 if bad else 0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of the wide-LSF path (an LSF whose halo does not fit a workgroup tile: host_abi.cpp launch_wide, kernels.hip
+"""Timing of the wide-LSF path (an LSF whose halo does not fit a workgroup tile: host_wide.cpp launch_wide, kernels.hip
 mcalf_wide_taps_kernel / mcalf_wide_conv_kernel) on the three geometries of tests/test_gpu_wide_lsf.py: ms per call of
 loglike_batch for 64 and 1024 live points, and what that is per live point and per tap x pixel.
     python tools/wide_lsf_timing.py        (GPU box)"""
