@@ -20,7 +20,10 @@ constexpr int kTabPad = VT_NTOT + 7;    // folded table in LDS: zone0 / zoneF sh
 constexpr int kZ0Lds = VT_Z0_OFF + 1;
 constexpr int kZFLds = VT_ZF_OFF + 2;
 constexpr int kLineLds = kZFLds + VT_FDEG + 1;   // [uthr, A, B] of the line, right behind its zone-F coefficients: the
-                                                 // node pass reads all ten doubles off ONE base address (5 x ds_read_b128)
+                                                 // node pass reads all ten doubles off ONE base address (5 x ds_read_b128).
+                                                 // Single-tile contexts behind a set-up: [W, A, B], W the line's 64-bit
+                                                 // segment-mask word (bit 8 i + v: segment 8 v + i is interpolated), which
+                                                 // the set-up leaves in slot 7 of the record in place of uthr
 static_assert(kLineLds + 3 <= kTabPad && (kLineLds % 2) == 1, "line constants pair up with the last zone-F coefficient");
 // Lines folded per workgroup barrier of the component loop: 4 or 5, chosen per context (whichever needs fewer
 // barriers for the context's largest line count; measured on MI355X: config C, 20-24 lines, -0.8 % with 5;

@@ -169,21 +169,62 @@ __device__ __forceinline__ void add_inplace(double& acc, double a) {
 }
 
 // tau[j] += K H(u_j, y) for the thread's kPpt pixels and one (component,line); `tab` is the line's
-// folded table in LDS (coefficients, then the line's threshold and the (A, B) of u = nu A - B).
+// folded table in LDS (coefficients, then the line's threshold -- or its segment-mask word -- and the (A, B) of u = nu A - B).
+//
+// kPreMask (single-tile spectra behind a set-up kernel or a streaming set-up phase): the set-up has classified the
+// line's 64 segments already (segment_masks) and the word W sits where the threshold does otherwise.  Pixels and
+// nodes are then owned DIFFERENTLY: wave `wv` still evaluates the pixels of segments wv, wv + 8, .. (interleaved, which
+// balances the direct work over the waves) -- byte wv of W, bit j = its slot j is interpolated -- but holds the nodes
+// of the ADJACENT segments 8 wv .. 8 wv + 7 -- bits 8 i of W >> wv.  A line's core and near wings cover a few adjacent
+// segments: the wing zones of the node pass, and often the node pass itself, then concern one or two waves per line
+// instead of nearly all of them, and no wave computes a mask.
+template <bool kPreMask>
 __device__ __forceinline__ void eval_line(const double* __restrict__ tab,
                                           const double (&nu)[kPpt], double (&tau)[kPpt], double nuNode,
-                                          double& farNode, unsigned long long segOk) {
+                                          double& farNode, unsigned long long segOk, int wv) {
     const double A = tab[kLineLds + 1], B = tab[kLineLds + 2];
     double cF[VT_FDEG + 1];
 #pragma unroll
     for (int k = 0; k <= VT_FDEG; ++k) cF[k] = tab[kZFLds + k];
+    // The node arithmetic of a wave whose node mask `done` (bit 8 j: segment j of the wave's nodes is interpolated)
+    // is not empty.
+    auto node_pass = [&](unsigned long long done, double x2n, double t) {
+        // byte j -> 0xFF: one bit per lane.  On 32-bit halves (no carry can cross: 0x01010101 * 0xFF = 0xFFFFFFFF),
+        // which is two scalar multiplies instead of a 64-bit one.
+        const unsigned long long lanes = ((unsigned long long)((unsigned)(done >> 32) * 0xFFu) << 32) | ((unsigned)done * 0xFFu);
+        const bool mine = __builtin_amdgcn_inverse_ballot_w64(lanes);   // the scalar mask IS the lane predicate
+        double P;
+        if (!mine || x2n >= kX2Far) {                         // (lanes of directly evaluated segments never need a wing zone)
+            P = cF[VT_FDEG];
+#pragma unroll
+            for (int k = VT_FDEG - 1; k >= 0; --k) P = fma(P, t, cF[k]);
+        } else {
+            const bool z0 = x2n >= kX2Wing;
+            const double sv = z0 ? t : fma(t, VT_Z1_A, VT_Z1_B);
+            const double* cw = tab + (z0 ? kZ0Lds : VT_Z1_OFF);
+            P = cw[VT_WDEG];
+#pragma unroll
+            for (int k = VT_WDEG - 1; k >= 0; --k) P = fma(P, sv, cw[k]);
+        }
+        fmac_inplace(farNode, mine ? t : 0.0, P);
+    };
     // Node pass.  Lane l holds node (l & 7) of the wave's segment (l >> 3).  A segment whose eight
     // nodes (both end pixels included, u monotonic along it) all have u >= uthr, or all u <= -uthr,
     // is wing (|u| >= x_c: no exp(-u^2)) for this line everywhere: its contribution is evaluated at the nodes only and
     // interpolated to the 64 pixels once, after the component loop.  `done` has bit 8 j set when
     // segment j was handled that way.
     unsigned long long done = 0;
-    if (kFarInterp) {
+    unsigned pix = 0;                                         // kPreMask: bit j = the wave's PIXEL slot j is interpolated
+    if (kFarInterp && kPreMask) {
+        const unsigned long long W = uniform64(__builtin_bit_cast(unsigned long long, tab[kLineLds]));
+        pix = (unsigned)(W >> (8 * wv)) & 0xFFu;
+        const unsigned long long nodes = (W >> wv) & 0x0101010101010101ull;
+        if (nodes != 0) {                                     // wave-uniform
+            const double un = fma(nuNode, A, -B);
+            const double x2n = un * un;
+            node_pass(nodes, x2n, fast_rcp(fmax(x2n, 4.0)));  // (the same operations on the same operands as below)
+        }
+    } else if (kFarInterp) {
         const double uthr = tab[kLineLds];
         const double un = fma(nuNode, A, -B);
         // issued ahead of the scalar mask chain below, which then runs in the shadow of the reciprocal
@@ -198,26 +239,7 @@ __device__ __forceinline__ void eval_line(const double* __restrict__ tab,
         mp &= mp >> 7;                                        // bit 8j = first and last node
         mn &= mn >> 7;
         done = uniform64((mp | mn) & segOk);                 // (segOk carries bits 8j only, so `done` does too)
-        if (done != 0) {                                      // wave-uniform
-            // byte j -> 0xFF: one bit per lane.  On 32-bit halves (no carry can cross: 0x01010101 * 0xFF = 0xFFFFFFFF),
-            // which is two scalar multiplies instead of a 64-bit one.
-            const unsigned long long lanes = ((unsigned long long)((unsigned)(done >> 32) * 0xFFu) << 32) | ((unsigned)done * 0xFFu);
-            const bool mine = __builtin_amdgcn_inverse_ballot_w64(lanes);   // the scalar mask IS the lane predicate
-            double P;
-            if (!mine || x2n >= kX2Far) {                         // (lanes of directly evaluated segments never need a wing zone)
-                P = cF[VT_FDEG];
-#pragma unroll
-                for (int k = VT_FDEG - 1; k >= 0; --k) P = fma(P, t, cF[k]);
-            } else {
-                const bool z0 = x2n >= kX2Wing;
-                const double sv = z0 ? t : fma(t, VT_Z1_A, VT_Z1_B);
-                const double* cw = tab + (z0 ? kZ0Lds : VT_Z1_OFF);
-                P = cw[VT_WDEG];
-#pragma unroll
-                for (int k = VT_WDEG - 1; k >= 0; --k) P = fma(P, sv, cw[k]);
-            }
-            fmac_inplace(farNode, mine ? t : 0.0, P);
-        }
+        if (done != 0) node_pass(done, x2n, t);               // wave-uniform
     }
     // Tested on 32-bit halves (one s_bitcmp1_b32 + branch per segment), four segments at a time first: a line's
     // core covers one or two ADJACENT segments of a wave, so one half of the eight is usually interpolated throughout.
@@ -225,11 +247,12 @@ __device__ __forceinline__ void eval_line(const double* __restrict__ tab,
 #pragma unroll
     for (int h = 0; h < kPpt / 4; ++h) {
     const unsigned dh = h ? doneHi : doneLo;
-    if (dh == 0x01010101u) continue;
+    if (kPreMask ? ((pix >> (4 * h)) & 0xFu) == 0xFu : dh == 0x01010101u) continue;
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
         const int j = 4 * h + jj;
-        if (__builtin_expect(((dh >> (8 * jj)) & 1u) != 0u, 1)) continue;   // whole segment interpolated (wave-uniform, the usual case)
+        // whole segment interpolated (wave-uniform, the usual case)
+        if (__builtin_expect((kPreMask ? (pix >> j) & 1u : (dh >> (8 * jj)) & 1u) != 0u, 1)) continue;
         const double u = fma(nu[j], A, -B);
         const double x2 = u * u;
         // Every branch leaves (t, P) with contribution t * P, and the running optical depth is updated at ONE
@@ -347,11 +370,48 @@ __device__ void build_order(const KArgs& a, long batch) {
 // The set-up of live point s by ONE wave (`lane` = 0..63): decode, records, taps, header, written through the given
 // pointers -- the context's workspaces in HBM (mcalf_sample_kernel) or the workgroup's own LDS (the one-launch
 // variant of the fused kernel that small calls use).  One body, so both give the same bits.
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, lane), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), lane);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// Segment-mask words of the records a wave holds one per lane (`have`: the lanes whose record is in use), for
+// eval_line<true>: bit 8 i + v of a record's word is set when segment 8 v + i of the (single) tile is interpolated
+// for that line -- both end pixels at u >= uthr or both at u <= -uthr, with eval_line's own fma and comparisons on the
+// values its node lanes 0 and 7 load, so the classification is the one-launch variant's bit for bit -- and the
+// context allows it (segok).  Lane l tests segment 8 (l & 7) + (l >> 3) of one record at a time -- nuLo / nuHi are that
+// segment's first and last pixel frequency, okW the lanes whose segment may be interpolated -- so that the ballots ARE
+// the word.  All 64 lanes must be active.  uthr = 0 (general-path and zero-strength records) gives every allowed
+// segment, uthr = inf or NaN none, as the comparisons do in the loop.
+__device__ __forceinline__ double segment_masks(const double (&rec)[kRecStride], int lane, unsigned long long have, double nuLo,
+                                                double nuHi, unsigned long long okW) {
+    unsigned long long word = 0;
+    for (unsigned long long todo = have; todo != 0; todo &= todo - 1) {       // (wave-uniform)
+        const int r = __builtin_ctzll(todo);
+        const double A = readlane_f64(rec[0], r), B = readlane_f64(rec[1], r), uthr = readlane_f64(rec[7], r);
+        const double u0 = fma(nuLo, A, -B), u1 = fma(nuHi, A, -B);
+        const unsigned long long mp = __builtin_amdgcn_ballot_w64(u0 >= uthr) & __builtin_amdgcn_ballot_w64(u1 >= uthr);
+        const unsigned long long mn = __builtin_amdgcn_ballot_w64(u0 <= -uthr) & __builtin_amdgcn_ballot_w64(u1 <= -uthr);
+        const unsigned long long w = (mp | mn) & okW;
+        if (lane == r) word = w;
+    }
+    return __builtin_bit_cast(double, word);
+}
+
+// segMasks: the records carry their segment-mask word in slot 7 instead of the threshold (the set-up kernel and the
+// streaming set-up phase of single-tile contexts, whose fused kernel is eval_line<true>); the one-launch variant, the
+// resident kernel and tiled contexts leave the threshold there and compute nothing more.
 template <bool kZeroPad>
 __device__ __forceinline__ void setup_sample(const KArgs& a, long s, int lane, double* recs, double* taps, bool writeTaps,
-                                             SampleHdr* hdrOut, bool writeTheta) {
+                                             SampleHdr* hdrOut, bool writeTheta, bool segMasks) {
     const int rowlen = (a.mode == kModeOneComp) ? 5 : a.ndim;
     const double* p = a.P + (size_t)s * rowlen;
+    // (segment masks: this lane's two pixel frequencies and the tile's interpolable segments go out with the row's loads)
+    const int mseg = 8 * (lane & 7) + (lane >> 3);
+    double nuLo = 0.0, nuHi = 0.0;
+    unsigned long long tileOk = 0;
+    if (segMasks) { nuLo = a.nu[64 * mseg]; nuHi = a.nu[64 * mseg + 63]; tileOk = a.segok[0]; }
     // ---- 1. decode the parameter vector ---------------------------------------------------
     double R, cont;
     int nc, nfill_eff;
@@ -380,7 +440,11 @@ __device__ __forceinline__ void setup_sample(const KArgs& a, long s, int lane, d
     const int nTargetSlots = (a.mode == kModeOneComp) ? nl_eff : a.ncompmax * a.nlines;
     const int nSlots = nTargetSlots + ((a.mode == kModeOneComp) ? 0 : a.nfill);
     int ngenLane = 0;
-    for (int slot = lane; slot < nSlots; slot += 64) {
+    // (segment masks: whole rounds of 64 -- the lanes past the last slot repeat it, write nothing and serve the ballots)
+    const int nSlotsRun = segMasks ? (nSlots + 63) & ~63 : nSlots;
+    for (int slot0 = lane; slot0 < nSlotsRun; slot0 += 64) {
+        const bool spare = segMasks && slot0 >= nSlots;
+        const int slot = spare ? nSlots - 1 : slot0;
         double logN, z, b;
         const LineDev* ln;
         int dst;                                    // index in the compacted record list, -1: inactive
@@ -403,8 +467,12 @@ __device__ __forceinline__ void setup_sample(const KArgs& a, long s, int lane, d
             ln = a.lines + a.nlines;
             dst = (nfill_eff > 0) ? nc * a.nlines + k : -1;
         }
+        if (spare) dst = -1;
         double rec[kRecStride];
         build_line_record(rec, logN, z, b, *ln, a.dnu_seg);
+        if (segMasks)
+            rec[7] = segment_masks(rec, lane, __builtin_amdgcn_ballot_w64(dst >= 0), nuLo, nuHi,
+                                   __builtin_amdgcn_ballot_w64(((tileOk >> mseg) & 1ULL) != 0));
         ngenLane += __popcll(__ballot(dst >= 0 && rec[6] != 0.0));        // (wave-uniform count)
         if (dst >= 0) {
 #pragma unroll
@@ -553,7 +621,8 @@ __global__ __launch_bounds__(kSetupBlockMax) void mcalf_sample_kernel(const KArg
     const int lane = threadIdx.x & 63;
     if (s == 0 && lane == 0) *a.queue = 0u;          // item queue of the fused kernel that follows on the stream
     setup_sample<kZeroPad>(a, s, lane, a.recs + (size_t)s * a.ncl_cap * kRecStride,
-                           a.taps + (a.taps_shared ? 0 : (size_t)s * (2 * a.n_cap + 8)), !a.taps_shared || s == 0, a.hdr + s, true);
+                           a.taps + (a.taps_shared ? 0 : (size_t)s * (2 * a.n_cap + 8)), !a.taps_shared || s == 0, a.hdr + s, true,
+                           a.selfhalo != 0);
 }
 
 // Lines outside the fast path's damping range (flag != 0; none for physical resonance lines).  Kept out
@@ -582,7 +651,7 @@ __device__ __forceinline__ void eval_general_lines(const double* __restrict__ sR
 // coalesced, all loads of the claim in flight at once, ONE PCIe round trip instead of setup_sample's two or three
 // dependent ones -- and set up from the copy.  Claims are dynamic on purpose: a row is owned by a workgroup that is
 // running, never by one that waits for a slot.
-template <bool kZeroPad>
+template <bool kZeroPad, bool kSelfHalo>
 __device__ __forceinline__ void stream_setup_phase(const KArgs& a, int tid, int x, int* sClaim) {
     const int lane = tid & 63, wave = tid >> 6;
     constexpr int nx = kXcds;
@@ -643,7 +712,8 @@ __device__ __forceinline__ void stream_setup_phase(const KArgs& a, int tid, int 
             if (r >= a.nrows) continue;
             SampleHdr* hdrp = reinterpret_cast<SampleHdr*>(reinterpret_cast<double*>(a.hdr) + (size_t)r * a.hdr_stride);
             if (ok) {
-                setup_sample<kZeroPad>(as, (long)r, lane, a.recs + (size_t)r * a.rec_stride, a.taps + (size_t)r * a.tap_stride, true, hdrp, true);
+                setup_sample<kZeroPad>(as, (long)r, lane, a.recs + (size_t)r * a.rec_stride, a.taps + (size_t)r * a.tap_stride, true, hdrp, true,
+                                       kSelfHalo);
             } else if (lane == 0) {                      // gave up on the host: a row nobody will mistake for a result
                 SampleHdr h;
                 h.cont = 0.0; h.bot = 1.0; h.ncl = 0; h.n = 0; h.bad = 1; h.ngeneral = 0;
@@ -752,7 +822,12 @@ __device__ __forceinline__ void request_item(const KArgs& a, int w, int tid, Ite
     }
     L.nuNode = 0.0;
     L.tileMask = 0;
-    if (kFarInterp) {
+    if (kFarInterp && selfHalo && !kInline) {
+        // segment masks from the set-up (eval_line<true>): the wave holds the nodes of the ADJACENT segments 8 wv .. 8 wv + 7,
+        // and which of them are interpolated comes with each line
+        const int wv = tid >> 6, ln = tid & 63;
+        L.nuNode = a.nu[kBlock * wv + 64 * (ln >> 3) + VT_INTERP_NODES[ln & 7]];
+    } else if (kFarInterp) {
         const int wv = tid >> 6, ln = tid & 63;
         int e = ext0 + 64 * wv + kBlock * (ln >> 3) + VT_INTERP_NODES[ln & 7];
         if (!selfHalo && (e < 0 || e >= a.npix)) { e %= npixW; if (e < 0) e += npixW; }   // such segments are never interpolated
@@ -791,6 +866,9 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
     constexpr int kTRegs = (VT_NY * VT_NTOT + kBlock - 1) / kBlock;
     constexpr int kRecRegs = 2;                        // covers ncl_cap <= 128 without a second trip
     constexpr bool selfHalo = kSelfHalo;               // (a.selfhalo chooses the instantiation on the host)
+    // the records carry segment-mask words (setup_sample(..., segMasks)) and the nodes sit on adjacent segments: eval_line<true>
+    constexpr bool kPreMask = kSelfHalo && !kInline;
+    static_assert(kLinesPerSync * kTabPad >= kBlock, "the node sums fit the idle half of the folded tables");
     if (kFarInterp) sWt[(tid0 & 7) * 64 + (tid0 >> 3)] = a.wtab[tid0];      // kBlock == 64 * VT_INODES
     const int recTotal = a.ncl_cap * kRecStride, tapTotal = 2 * a.n_cap + 8;
     // streaming launch: this workgroup's XCD, whose queue hands out LOCAL tickets over the XCD's own live points
@@ -869,17 +947,18 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
         const double nuNode = L.nuNode;
         double farNode = 0.0;
         unsigned long long segOk = 0;
-        if (kFarInterp) {
+        if (kFarInterp && !kPreMask) {                    // (kPreMask: the mask words have it folded in)
             const int wv = tid >> 6;
 #pragma unroll
             for (int j = 0; j < kPpt; ++j) segOk |= ((L.tileMask >> (wv + 8 * j)) & 1ULL) << (8 * j);
             segOk = uniform64(segOk);
         }
+        const int wvU = kPreMask ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;   // the wave's index, as a scalar
         SampleHdr hd;
         SampleHdr* sHdr = reinterpret_cast<SampleHdr*>(sRed + 2 * kWaves);   // (one-launch variant; the slot is scratch until the reduction)
         static_assert(sizeof(SampleHdr) <= kWaves * sizeof(double), "header fits the scratch slot");
         if (kInline) {
-            if (tid < 64) setup_sample<kZeroPad>(a, s, tid, sRec, sW, true, sHdr, tileIdx == 0);
+            if (tid < 64) setup_sample<kZeroPad>(a, s, tid, sRec, sW, true, sHdr, tileIdx == 0, false);
         } else {
             hd = L.hd;
 #pragma unroll
@@ -973,7 +1052,8 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
                 for (int l = 0; l < kLinesPerSync; ++l) tabs[l * kTabPad + coefPos] = fc[l] * fs[l];   // = fold_coef()
             } else if (tid >= kBlock - 64 && tid < kBlock - 64 + 3) {
                 // the last wave folds nothing: three of its lanes copy each line's [uthr, A, B] behind its coefficients
-                const int which = tid - (kBlock - 64);                                 // 0: uthr, 1: A, 2: B
+                // (kPreMask: slot 7 of the record holds the line's segment-mask word instead -- copied as the 8 bytes it is)
+                const int which = tid - (kBlock - 64);                                 // 0: uthr / mask word, 1: A, 2: B
                 const int src = (which == 0) ? 7 : which - 1;
 #pragma unroll
                 for (int l = 0; l < kLinesPerSync; ++l)
@@ -984,18 +1064,24 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
             // one copy of the (large) per-line body: keeps the loop inside the instruction cache
             const int lmax = __builtin_amdgcn_readfirstlane(min(kLinesPerSync, ncl_run - cl0));   // (kept scalar)
 #pragma unroll 1
-            for (int l = 0; l < lmax; ++l) eval_line(tabs + l * kTabPad, nu, tau, nuNode, farNode, segOk);
+            for (int l = 0; l < lmax; ++l) eval_line<kPreMask>(tabs + l * kTabPad, nu, tau, nuNode, farNode, segOk, wvU);
         }
         if (hd.ngeneral > 0 && ncl_run > 0) eval_general_lines(sRec, ncl, nu, tau);
         __builtin_amdgcn_s_setprio(0);
         // Interpolate the far-wing node sums to the pixels (tau[j] += sum_k W[lane][k] F[segment j][node k]),
         // then flux = exp(-tau) into the LDS tile.  The node sums travel through the (now dead) folded-table
         // region, one 64-entry row per wave; the tile holds only the sample's own halo n (<= n_cap).
+        // kPreMask: the sums of pixel wave w's slot j (segment w + 8 j) are held by NODE wave j, lanes 8 w .. 8 w + 7, so
+        // they cross waves.  They are stored AHEAD of the barrier, into the half of the double-buffered tables that the
+        // last group of lines did not use (`buf` by now): nobody has read it since the barrier of that group, which
+        // every wave passed after its last read of it.
         double wrow[VT_INODES];
-        double* sFar = sTab + (tid >> 6) * 64;
+        double* sFar = kPreMask ? sTab + buf * (kLinesPerSync * kTabPad) + 8 * (tid >> 6) : sTab + (tid >> 6) * 64;
+        constexpr int kFarSlot = kPreMask ? 64 : 8;        // doubles between the node sums of a wave's consecutive pixel slots
         if (kFarInterp) {
+            if (kPreMask) sTab[buf * (kLinesPerSync * kTabPad) + tid] = farNode;
             __syncthreads();                               // every wave is done reading the folded tables
-            sFar[tid & 63] = farNode;
+            if (!kPreMask) sFar[tid & 63] = farNode;
 #pragma unroll
             for (int k = 0; k < VT_INODES; ++k) wrow[k] = sWt[k * 64 + (tid & 63)];
         }
@@ -1021,7 +1107,7 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
                 if (kFarInterp) {
                     double add = 0.0;
 #pragma unroll
-                    for (int k = 0; k < VT_INODES; ++k) add = fma(wrow[k], sFar[8 * j + k], add);
+                    for (int k = 0; k < VT_INODES; ++k) add = fma(wrow[k], sFar[kFarSlot * j + k], add);
                     tj += add;
                 }
                 fl[jj] = exp_neg(tj);                      // :377 (product of exp == exp of sum)
@@ -1217,7 +1303,7 @@ __global__ __launch_bounds__(kBlock, kMinWaves) void mcalf_fused_kernel(const KA
     static_assert(!(kInline && kStream), "the one-launch variant of small calls has no queue to stream through");
     extern __shared__ __align__(16) double smem[];
     if constexpr (kStream) {
-        stream_setup_phase<kZeroPad>(a, threadIdx.x, xcd_id(), reinterpret_cast<int*>(smem));
+        stream_setup_phase<kZeroPad, kSelfHalo>(a, threadIdx.x, xcd_id(), reinterpret_cast<int*>(smem));
 
         // The item loop reads its arguments afresh from the kernel-argument segment (through a pointer the compiler
         // cannot see through): their live ranges then start HERE, as in the two-kernel variant.  With one set of
