@@ -80,7 +80,9 @@ extern "C" {
                                     with a vector)
                                     (added within 9, nothing else changed: mcalf_loglike_hvp_batch[_device], the product of
                                     logL's exact Hessian with a vector;
-                                    mcalf_eqw_batch[_device], batched equivalent widths) */
+                                    mcalf_eqw_batch[_device], batched equivalent widths;
+                                    mcalf_model_band_batch[_device], per-pixel mean, variance and quantiles of the model
+                                    over the rows of a chain) */
 
 enum {
     MCALF_OK = 0,
@@ -389,6 +391,40 @@ int mcalf_eqw_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t inde
  * allocates and synchronises nothing. */
 int mcalf_eqw_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, double* dWcomp, double* dWblend,
                            void* stream);
+
+/* Per-pixel posterior bands of the model over the rows of a chain, on the device, without a spectrum reaching the host (the
+ * reference's plot pass overplots 100 sampled spectra instead, mcalf/cli.py:398-418).  With M[i, :] = mcalf_model_batch(P[i],
+ * targonly) under the context's conv_mode -- the same kernels, the same bits, wide LSFs and tiled spectra included -- and,
+ * for pixel k, the rows whose M[i, k] is not NaN (np.nanmean / np.nanvar / np.nanquantile):
+ *   nvalid[k]   [npix]      how many such rows there are
+ *   mean[k]     [npix]      their arithmetic mean
+ *   var[k]      [npix]      their population variance (ddof 0), in TWO passes: the mean first, then the centred squares (a
+ *                           continuum pixel is 1 with a spread of 1e-10: E[x^2] - mean^2 would be rounding noise there)
+ *   Q[j, k]     [nq][npix]  the q[j]-quantile under numpy's default "linear" rule: h = (nvalid - 1) q[j], lo = x_(floor h),
+ *                           hi = x_(min(floor h + 1, nvalid - 1)), Q = lo + (hi - lo) (h - floor h), x_(r) the r-th smallest
+ *                           valid value -- an EXACT selection among the stored values (radix select), no histogram estimate
+ * A pixel with nvalid == 0 has NaN in mean, var and Q.  Any of mean, var, Q, nvalid may be NULL, not all; Q == NULL exactly
+ * when nq == 0; nq <= 16; every q[j] finite and in [0, 1].  The conventions are the derivative entries': a row's numerical
+ * failure is a value (an all-NaN row simply does not count); no floating-point atomics, every floating-point sum in ONE order
+ * that depends on neither the batch, the grid nor the outputs requested (rows in blocks of 256, a block's rows in row order
+ * per 64, the blocks in block order; the radix histograms are integer counters); two calls on the same input give the same bits.
+ * Memory: the statistic needs every row resident.  The host entry allocates the batch x npix matrix on the device and
+ * RELEASES it before it returns; the context keeps per-pixel buffers and batch / 256 rows of partial sums only.
+ * batch * npix * 8 bytes above 4 GiB is MCALF_ERR_RANGE (the message names the largest batch for this spectrum: thin the
+ * chain), before any device work and before a row of P is read.  MCALF_ERR_INVALID, likewise before any device work, for: a
+ * NULL context, batch < 0, a NULL P with batch > 0, all outputs NULL, nq outside [0, 16], nq > 0 with a NULL q or Q (or Q
+ * with nq == 0), a q[j] not finite or outside [0, 1], targonly outside {0, 1}.  batch == 0 fills the requested outputs
+ * with NaN and nvalid with 0.  Host pointers, synchronous.  A multi-device context runs the whole call on its first device
+ * entry -- all rows have to meet on one device -- so the result is bit for bit a single-device context's. */
+int mcalf_model_band_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t targonly, const double* q, int32_t nq,
+                           double* mean, double* var, double* Q, int64_t* nvalid);
+/* Same, device pointers, on the caller's stream (single-device contexts).  q is a HOST array, read during the call (its
+ * values travel in the kernels' argument block: nothing of the caller's is read after the call returns).  dM is the caller's
+ * [batch][npix] workspace (NULL with batch > 0: MCALF_ERR_INVALID); ON RETURN dM HOLDS THE MODEL ROWS, exactly what
+ * mcalf_model_batch_device(dP, batch, targonly) writes.  After one call of the same or a larger batch and nq it allocates
+ * and synchronises nothing. */
+int mcalf_model_band_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t targonly, const double* q, int32_t nq,
+                                  double* dM, double* dmean, double* dvar, double* dQ, int64_t* dnvalid, void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -146,6 +146,10 @@ SYMBOLS = {
     "mcalf_loglike_hvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_eqw_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcalf_eqw_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_model_band_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_model_band_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_eqw.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -283,6 +283,12 @@ struct mcalf_ctx {
     DevBuf<double> d_dlam;
     enum { kEbRecs, kEbPart, kEbP, kEbWcomp, kEbWblend, kEbCount };
     DevBuf<double> eb[kEbCount];
+    // The posterior-band entries (host_band.cpp), grown on demand: the per-block partials and counts, the per-pixel mean / count
+    // a call keeps for itself when the caller wants neither, the selected order statistics, and the host-pointer entry's staging
+    // (parameter rows in, the 3 + nq per-pixel rows out).  The [batch][npix] model matrix is NOT among them: the host entry
+    // releases it before it returns, the device entry is handed the caller's.
+    enum { kBbPart, kBbMean, kBbCount, kBbSel, kBbP, kBbOut, kBbBufs };
+    DevBuf<double> bb[kBbBufs];
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).

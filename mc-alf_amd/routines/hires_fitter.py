@@ -16,6 +16,7 @@ replaced by an explicit `linepars=` argument plus a tiny built-in table (`LINE_T
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import gc
 from typing import Optional, Sequence
@@ -23,6 +24,9 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import _lib
+
+# what als_fitter.model_band_batch returns: per-pixel mean, variance, quantiles [len(q), npix] and the count of non-NaN rows
+ModelBand = collections.namedtuple("ModelBand", "mean var quantiles nvalid")
 
 # (wrest [A], f, gamma [1/s]).  CIV: pinned by the reference's own test spectra
 # (SURVEY.md section 4).  HI 1215: Morton (2003), NOT pinned (linetools absent).
@@ -614,6 +618,27 @@ class als_fitter:
             cont = np.full(P.shape[0], _scalar(self.contval), dtype=float)
         w[used & ~(np.isfinite(cont) & (cont != 0))] = np.nan
         return w
+
+    def model_band_batch(self, P, q=(0.16, 0.5, 0.84), targonly=False):
+        """Where the chain `P` puts the model spectrum, per pixel, computed on the device (HIP kernels; no spectrum reaches
+        the host): `ModelBand(mean[npix], var[npix], quantiles[len(q), npix], nvalid[npix])` over the rows of
+        `model_batch(P, targonly)` that are not NaN at that pixel -- `np.nanmean`, `np.nanvar` (ddof 0, two passes) and
+        `np.nanquantile(..., method="linear")`, the quantiles exact selections among the stored values.  `nvalid` (int64)
+        counts those rows; a pixel without any is NaN in the other three.  `q=()` leaves the quantiles out (shape [0, npix]).
+        The [batch, npix] matrix lives on the device for the length of the call only; beyond 4 GiB the call is refused (thin
+        the chain).  The result does not depend on the device count of the context, and two calls give the same bits."""
+        P = self._rows(P, self.ndim)
+        qs = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=float)).reshape(-1))
+        npix = self.obj_wl.size
+        mean, var = np.empty(npix), np.empty(npix)
+        quant = np.empty((qs.size, npix))
+        nvalid = np.empty(npix, dtype=np.int64)
+        rc = self._lib.mcalf_model_band_batch(self._ctx, self._ptr(P), P.shape[0], int(bool(targonly)),
+                                              self._ptr(qs) if qs.size else None, qs.size, self._ptr(mean), self._ptr(var),
+                                              self._ptr(quant) if qs.size else None, self._ptr(nvalid))
+        if rc:
+            _lib.check(rc, self._ctx)
+        return ModelBand(mean, var, quant, nvalid)
 
     def calc_N_batch(self, P):
         """`calc_N(P[i], reference_indexing=False)` for every row ([batch]; host numpy, no kernel): log10 of the summed
