@@ -82,7 +82,9 @@ extern "C" {
                                     logL's exact Hessian with a vector;
                                     mcalf_eqw_batch[_device], batched equivalent widths;
                                     mcalf_model_band_batch[_device], per-pixel mean, variance and quantiles of the model
-                                    over the rows of a chain) */
+                                    over the rows of a chain;
+                                    mcalf_fisher_matvec_batch[_device], the Fisher product J^T W J v on the device, and
+                                    mcalf_maximize_batch[_device], batched Levenberg-Marquardt maximisation of logL) */
 
 enum {
     MCALF_OK = 0,
@@ -425,6 +427,63 @@ int mcalf_model_band_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32
  * and synchronises nothing. */
 int mcalf_model_band_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t targonly, const double* q, int32_t nq,
                                   double* dM, double* dmean, double* dvar, double* dQ, int64_t* dnvalid, void* stream);
+
+/* The Fisher product of the Gaussian likelihood, matrix-free and on the device: FV[i, :] = J(P[i])^T W J(P[i]) V[i, :], P, V
+ * and FV batch x ndim, row-major.  J is the model Jacobian of mcalf_model_jvp_batch; W = 1 / err^2 on the pixels whose logL term
+ * nansum keeps (finite flux, finite non-zero error) and 0 elsewhere -- a device array of the context, built by the first call.
+ * One call is one JVP pass, one per-pixel multiply dM <- W (.) dM and one VJP pass with dM as the cotangent, row block by row
+ * block inside a context-owned [rows][npix] workspace (rows * npix * 8 bytes within 384 MiB, at most 65535 rows): the
+ * [batch][npix] intermediate never leaves the device.  The result is bit for bit mcalf_model_vjp_batch(P, W * mcalf_model_jvp_batch(P, V)),
+ * and the conventions are those entries': ignored entries of V and exact-0 columns of FV (the ncomp slot, inactive (N, z, b), R /
+ * continuum the context fixes), an all-NaN row when R needs more taps than the context provisions, every reduction in a fixed
+ * order, a multi-device context cutting the rows as the gradient does.  MCALF_ERR_INVALID before any device work for a NULL
+ * context, batch < 0 or a NULL array with batch > 0; batch == 0 does nothing. */
+int mcalf_fisher_matvec_batch(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* FV);
+/* Same, device pointers, on the caller's stream (single-device contexts).  After one call of the same or a larger batch it
+ * allocates and synchronises nothing. */
+int mcalf_fisher_matvec_batch_device(mcalf_ctx* ctx, const double* dP, const double* dV, int64_t batch, double* dFV, void* stream);
+
+/* Batched Levenberg-Marquardt maximisation of logL: every row of P0 (batch x ndim) is polished independently to a maximum of
+ * logL -- exactly mcalf_loglike_batch's value -- over its continuous, active parameters inside the box of mcalf_set_prior
+ * (MCALF_ERR_INVALID if none is set, if a bound is not finite or if lo > hi).  Never changed: the ncomp slot (its bits are
+ * kept, a fractional 2.7 included) and the (N, z, b) of slots at or beyond the row's active count; R and the continuum move only
+ * where the context floats them.  The fit works in cube coordinates, s = hi - lo, u = (theta - lo) / s; s == 0 fixes a coordinate.
+ * Per row:
+ *   start   the continuous, active entries of P0 are clamped into the box; logL and its gradient G there.  A start whose logL
+ *           is not finite (asymmetric veto, R beyond the tap cap) or that has a NaN among those entries (nansum drops every
+ *           pixel of such a row: its logL is a finite 0) has status -1 and its row is returned as given.
+ *   pins    coordinate k does not move in this iteration if theta_k <= lo_k and G_k < 0, if theta_k >= hi_k and G_k > 0, or if
+ *           s_k == 0.  g_u = s (.) G with the pinned entries 0; all zero: status 2.
+ *   step    (A + lambda I) x = g_u by conjugate gradients from x = 0, A = s (.) J^T W J (.) s on the unpinned coordinates,
+ *           cg_iters iterations, one Fisher product (above) each; a row's CG stops early when p.(A + lambda I)p <= 0 or
+ *           r.r <= 1e-20 g_u.g_u.  Nothing dense is formed.
+ *   trial   T = clamp(theta + s (.) x, lo, hi); accepted iff logL(T) is finite and > logL(theta): theta <- T, lambda <-
+ *           max(lambda / 10, 1e-15), and status 1 if the gain is <= ftol (1 + |logL(T)|).  Rejected: lambda <- 10 lambda, status
+ *           3 once lambda exceeds 1e12; theta stays.
+ * status 0: max_iter outer iterations were run.  niter counts the outer iterations a row took a step in.  logL never decreases,
+ * and on return logL[i] is the likelihood of P[i] bit for bit (for a status -1 row: of its clamped start).  Rows run in lock
+ * step and finished rows are carried unchanged; every sum has one order (a wave per row, one fixed butterfly), so a row's bits
+ * depend on its own start and the options alone -- not on its batch, its position, the row block or the device count.
+ * A fit costs about (cg_iters + 1) Voigt passes per outer iteration and row. */
+typedef struct {
+    int32_t max_iter;        /* outer iterations, >= 0 (0: the clamped start, its logL, status 0 or -1, niter 0) */
+    int32_t cg_iters;        /* CG iterations per outer iteration; 0 = ndim */
+    int32_t rows_per_block;  /* 0 = rows * npix * 8 bytes within 384 MiB, at most 65535; else rows fitted together (bounds the workspace) */
+    int32_t reserved;
+    double lambda0;          /* initial damping, cube units, > 0 */
+    double ftol;             /* >= 0 */
+} mcalf_fit_opts;
+/* Host pointers, synchronous: P (batch x ndim), logL, status, niter (batch each) are outputs; P0 and P must not overlap.  After
+ * every outer iteration the call reads the count of live rows (4 bytes) and stops at 0.  A multi-device context cuts the rows
+ * as the gradient does.  All argument checks (NULL arrays, batch < 0, negative counts, lambda0 not finite or <= 0, ftol not
+ * finite or < 0, the prior box) come before any device work and name the argument.  batch == 0 does nothing. */
+int mcalf_maximize_batch(mcalf_ctx* ctx, const double* P0, int64_t batch, const mcalf_fit_opts* opts, double* P, double* logL,
+                         int32_t* status, int32_t* niter);
+/* Same, device pointers (opts is a host struct, read during the call), on the caller's stream (single-device contexts).  It
+ * runs max_iter iterations unconditionally and never synchronises; the bits are the host entry's.  After one call of the same
+ * or a larger batch and block size it allocates nothing. */
+int mcalf_maximize_batch_device(mcalf_ctx* ctx, const double* dP0, int64_t batch, const mcalf_fit_opts* opts, double* dP, double* dlogL,
+                                int32_t* dstatus, int32_t* dniter, void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

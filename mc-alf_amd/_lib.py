@@ -117,6 +117,21 @@ class mcalf_broker_t(C.Structure):
     ]
 
 
+class mcalf_fit_opts(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int32),
+        ("cg_iters", C.c_int32),
+        ("rows_per_block", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lambda0", C.c_double),
+        ("ftol", C.c_double),
+    ]
+
+
+# status of a row of mcalf_maximize_batch
+MCALF_FIT_MAXITER, MCALF_FIT_CONVERGED, MCALF_FIT_ZERO_GRADIENT, MCALF_FIT_LAMBDA, MCALF_FIT_BAD_START = 0, 1, 2, 3, -1
+
+
 # every symbol include/mcalf_hip.h declares: name -> (restype, argtypes)
 _PD = C.POINTER(C.c_double)
 _CTX = C.c_void_p
@@ -150,6 +165,11 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_model_band_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_fisher_matvec_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mcalf_fisher_matvec_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mcalf_maximize_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_maximize_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

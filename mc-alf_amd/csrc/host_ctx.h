@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_fit.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -24,6 +24,7 @@
 #include "../../include/mcalf_hip.h"
 #pragma GCC visibility pop
 #include "kernel_args.h"
+#include "grad_args.h"
 
 #define MCALF_STR_(x) #x
 #define MCALF_STR(x) MCALF_STR_(x)
@@ -289,6 +290,16 @@ struct mcalf_ctx {
     // releases it before it returns, the device entry is handed the caller's.
     enum { kBbPart, kBbMean, kBbCount, kBbSel, kBbP, kBbOut, kBbBufs };
     DevBuf<double> bb[kBbBufs];
+    // The Fisher product and the fit (host_fit.cpp), grown on demand.  d_fitw: W [npix] of the Fisher product, built by its first
+    // call (released with the context, after the resident evaluator has left).  kFbDM: the [rows][npix] workspace of one row block
+    // of a Fisher product; the per-row vectors [rows][ndim] and scalars [rows] of one row block of a fit; the host-pointer
+    // entries' staging.  fit_int: status, niter, CG-frozen flag [rows] each and the pins [rows][ndim]; d_fit_live: the counter
+    // of live rows the host entry reads after every outer iteration.
+    DevBuf<double> d_fitw;
+    enum { kFbDM, kFbT, kFbG, kFbGT, kFbGu, kFbX, kFbR, kFbPv, kFbV, kFbFV, kFbScal, kFbP0, kFbP, kFbL, kFbHostV, kFbHostFV, kFbCount };
+    DevBuf<double> fb[kFbCount];
+    DevBuf<int32_t> fit_int, fit_hst;       // (fit_hst: the host-pointer entry's status and niter rows)
+    DevBuf<unsigned int> d_fit_live;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -431,6 +442,22 @@ void stream_trace_report(mcalf_ctx* ctx);
 void resident_stop(mcalf_ctx* ctx);
 bool resident_serves(const mcalf_ctx* ctx, int mode, int64_t batch, int rowlen, bool from_cube);
 int resident_call(mcalf_ctx* ctx, const double* row, int rowlen, double* out);
+
+// ---- host_grad.cpp: the derivative products, for host_fit.cpp -----------------------------------------------------------
+// The device rows of one call: parameters [batch, ndim], the second input (V or Q; none for the gradient), the primary
+// output (G, dM or HV) and logL [batch] (NULL: the context's own buffer).
+struct Call { const double *P, *X; double *Y, *L; };
+struct Product {
+    const char* device_entry;     // the name its device-pointer entry reports
+    int nws;                      // its per-row workspaces are ctx->gb[0, nws); they also cut its passes
+    bool own_q;                   // false: `q` is the caller's array, no q workspace is grown (the passes are cut all the same)
+    bool logl, l_out;             // logL of the batch first (the veto rule); logL is an output of the entry too
+    bool has_x, x_pix, y_pix;     // a second input; X / Y rows are npix wide (else ndim)
+    GradKernel seq[8];            // the kernels of a pass in order, kGradKernelCount after the last
+    void (*bind)(GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t row0);   // the row pointers of the pass at row0 (P is the driver's)
+};
+extern const Product kProdGrad, kProdJvp, kProdVjp, kProdHvp;
+int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStream_t stream);   // product `p` over device rows, on `stream`
 
 // ---- host_eqw.cpp: the equivalent-width entries -------------------------------------------------------------------------
 int eqw_prepare(mcalf_ctx* ctx, const double* wl);     // mcalf_create: dlam on the device

@@ -58,42 +58,35 @@ GradArgs grad_args(const mcalf_ctx* ctx) {
     return a;
 }
 
-// The device rows of one call: parameters [batch, ndim], the second input (V or Q; none for the gradient), the primary
-// output (G, dM or HV) and logL [batch] (NULL: the context's own buffer).
-struct Call { const double *P, *X; double *Y, *L; };
+}  // namespace
 
-struct Product {
-    const char* device_entry;     // the name its device-pointer entry reports
-    int nws;                      // its per-row workspaces are ctx->gb[0, nws); they also cut its passes
-    bool own_q;                   // false: `q` is the caller's array, no q workspace is grown (the passes are cut all the same)
-    bool logl, l_out;             // logL of the batch first (the veto rule); logL is an output of the entry too
-    bool has_x, x_pix, y_pix;     // a second input; X / Y rows are npix wide (else ndim)
-    GradKernel seq[8];            // the kernels of a pass in order, kGradKernelCount after the last
-    void (*bind)(GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t row0);   // the row pointers of the pass at row0 (P is the driver's)
-};
-
-const Product kProdGrad = {"mcalf_loglike_grad_batch_device", mcalf_ctx::kGbShared, true, true, true, false, false, false,
+// (struct Call and struct Product: host_ctx.h -- host_fit.cpp runs these products too)
+extern const Product kProdGrad = {"mcalf_loglike_grad_batch_device", mcalf_ctx::kGbShared, true, true, true, false, false, false,
     {kGradSetup, kGradForward, kGradModel, kGradAdjoint, kGradDeriv, kGradFinalize, kGradKernelCount},
     [](GradArgs& a, const Call& c, size_t cell0, size_t, int64_t row0) { a.logL = c.L + row0; a.G = c.Y + cell0; }};
 // dM = J(P) V row by row: setup, the tangent Voigt pass, the convolutions.
-const Product kProdJvp = {"mcalf_model_jvp_batch_device", mcalf_ctx::kGbShared, true, false, false, true, false, true,
+extern const Product kProdJvp = {"mcalf_model_jvp_batch_device", mcalf_ctx::kGbShared, true, false, false, true, false, true,
     {kGradSetup, kGradJvpForward, kGradJvpModel, kGradKernelCount},
     [](GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t) { a.V = c.X + cell0; a.dM = c.Y + pix0; }};
 // G = J(P)^T Q row by row: the gradient's pass with the caller's cotangent rows as q (read only) and no logL.
-const Product kProdVjp = {"mcalf_model_vjp_batch_device", mcalf_ctx::kGbShared, false, false, false, true, true, false,
+extern const Product kProdVjp = {"mcalf_model_vjp_batch_device", mcalf_ctx::kGbShared, false, false, false, true, true, false,
     {kGradSetup, kGradForward, kGradVjpModel, kGradAdjoint, kGradDeriv, kGradVjpFinalize, kGradKernelCount},
     [](GradArgs& a, const Call& c, size_t cell0, size_t pix0, int64_t) { a.q = const_cast<double*>(c.X) + pix0; a.G = c.Y + cell0; }};
 // HV = (d2 logL / dtheta2)(P) V row by row: the taps' second derivative, the tangent Voigt pass, q / dq, g / dg, the
 // second-order Voigt pass and the gradient's finalize (logL, for its veto rule, stays in the context's buffer).
-const Product kProdHvp = {"mcalf_loglike_hvp_batch_device", mcalf_ctx::kGbHvp, true, true, false, true, false, false,
+extern const Product kProdHvp = {"mcalf_loglike_hvp_batch_device", mcalf_ctx::kGbHvp, true, true, false, true, false, false,
     {kGradSetup, kGradHvpTaps, kGradJvpForward, kGradHvpModel, kGradHvpAdjoint, kGradHvpDeriv, kGradFinalize, kGradKernelCount},
     [](GradArgs& a, const Call& c, size_t cell0, size_t, int64_t row0) { a.V = c.X + cell0; a.logL = c.L + row0; a.G = c.Y + cell0; }};
+
+namespace {
 
 dim3 grad_grid(GradKernel k, const GradArgs& a) {
     if (k < kGradFirstPixel) return dim3((unsigned)a.nrows);
     if (k < kGradFirstCell) return dim3((unsigned)a.ntiles, (unsigned)a.nrows);
     return dim3((unsigned)(((int64_t)a.nrows * a.ndim + kGradBlock - 1) / kGradBlock));
 }
+
+}  // namespace
 
 // Product `p` over a batch, all on `stream`: its workspaces for one pass (grown once: a later call of as many rows or fewer
 // allocates nothing), logL of the batch where it needs one (the likelihood's launch, which sizes its own workspaces), then
@@ -125,6 +118,8 @@ int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStre
     }
     return MCALF_OK;
 }
+
+namespace {
 
 int run_device(mcalf_ctx* ctx, const Product& p, const Call& c, int64_t batch, void* stream) {
     if (!ctx || batch < 0 || (batch > 0 && (!c.P || !c.Y || (p.has_x && !c.X) || (p.l_out && !c.L))))

@@ -375,11 +375,7 @@ class als_fitter:
         per-sample set-up kernel.  `int_ncomp=False` gives the MultiNest flavour (:211-216)."""
         cubes = self._rows(cubes, self.ndim)
         pd = C.POINTER(C.c_double)
-        key = bool(int_ncomp)
-        if getattr(self, "_prior_key", None) != key:
-            _lib.check(self._lib.mcalf_set_prior(self._ctx, self._lo.ctypes.data_as(pd),
-                                                 self._hi.ctypes.data_as(pd), int(key)), self._ctx)
-            self._prior_key = key
+        self._ensure_prior(int_ncomp)
         logL = np.empty(cubes.shape[0])
         theta = np.empty_like(cubes) if return_theta else None
         _lib.check(self._lib.mcalf_loglike_cube_batch(
@@ -478,14 +474,56 @@ class als_fitter:
         are exactly 0; a row whose R needs more taps than the context provisions is all NaN."""
         return self._deriv_call(self._lib.mcalf_model_vjp_batch, P, Q, self.obj_wl.size, out, self.ndim, "Q")
 
-    def fisher_matvec_batch(self, P, V):
-        """(J^T W J) V[i] per row, the Fisher matrix of the Gaussian likelihood at P[i] applied to V[i], matrix-free:
-        one `model_jvp_batch` and one `model_vjp_batch`.  W = 1 / err^2 on the pixels whose logL term np.nansum keeps
-        (finite flux, finite non-zero error) and 0 elsewhere."""
-        with np.errstate(divide="ignore", invalid="ignore"):
-            w = 1.0 / np.asarray(self.obj_noise, dtype=float) ** 2
-            w = np.where(np.isnan(w * np.asarray(self.obj, dtype=float) ** 2 - np.log(w)), 0.0, w)
-        return self.model_vjp_batch(P, w * self.model_jvp_batch(P, V))
+    def fisher_matvec_batch(self, P, V, out=None):
+        """(J^T W J) V[i] per row, the Fisher matrix of the Gaussian likelihood at P[i] applied to V[i], matrix-free and on
+        the device (`mcalf_fisher_matvec_batch`): one JVP pass, a per-pixel multiply by W and one VJP pass, without the
+        [batch, npix] intermediate leaving the device -- bit for bit `model_vjp_batch(P, W * model_jvp_batch(P, V))`.
+        W = 1 / err^2 on the pixels whose logL term np.nansum keeps (finite flux, finite non-zero error) and 0 elsewhere."""
+        return self._deriv_call(self._lib.mcalf_fisher_matvec_batch, P, V, self.ndim, out, self.ndim, "V")
+
+    def _ensure_prior(self, int_ncomp=None):
+        """The prior box on the device (`mcalf_set_prior`), sent once per ncomp flavour.  `int_ncomp=None`: any flavour
+        that is already there will do (the box is the same), the PolyChord one if none is."""
+        have = getattr(self, "_prior_key", None)
+        key = (True if have is None else have) if int_ncomp is None else bool(int_ncomp)
+        if have != key:
+            pd = C.POINTER(C.c_double)
+            _lib.check(self._lib.mcalf_set_prior(self._ctx, self._lo.ctypes.data_as(pd),
+                                                 self._hi.ctypes.data_as(pd), int(key)), self._ctx)
+            self._prior_key = key
+
+    def maximize_batch(self, P0, max_iter=50, cg_iters=None, lambda0=1e-3, ftol=1e-10, rows_per_block=0):
+        """(P, logL, status, niter): every row of P0 polished to a maximum of logL inside the prior box by a batched
+        Levenberg-Marquardt iteration on the device (`mcalf_maximize_batch`; HIP kernels, nothing dense is formed: the
+        damped normal equations are solved by `cg_iters` conjugate-gradient iterations, one Fisher product each;
+        None = ndim).
+
+        The ncomp slot and the (N, z, b) of slots at or beyond a row's active count are returned bit for bit; the other
+        entries of a start are clamped into the box first.  logL[i] is `loglike_batch(P)[i]` bit for bit and never
+        below the clamped start's.  status: 1 converged (the last accepted gain is <= ftol (1 + |logL|)), 0 `max_iter`
+        reached, 2 zero projected gradient, 3 damping beyond 1e12, -1 the start's logL is not finite (the row comes
+        back as given).  niter: outer iterations the row took a step in.  `rows_per_block` bounds the rows fitted together
+        (0: the library's rule); a row's result does not depend on it."""
+        P0 = self._rows(P0, self.ndim)
+        n = P0.shape[0]
+        self._ensure_prior()
+        opts = _lib.mcalf_fit_opts(int(max_iter), 0 if cg_iters is None else int(cg_iters), int(rows_per_block), 0,
+                                   float(lambda0), float(ftol))
+        if cg_iters is not None and int(cg_iters) <= 0:
+            raise ValueError("cg_iters must be positive (None: ndim)")
+        P = np.empty_like(P0)
+        logL = np.empty(n)
+        status = np.empty(n, dtype=np.int32)
+        niter = np.empty(n, dtype=np.int32)
+        _lib.check(self._lib.mcalf_maximize_batch(self._ctx, self._ptr(P0), n, C.addressof(opts), self._ptr(P), self._ptr(logL),
+                                                  status.ctypes.data, niter.ctypes.data), self._ctx)
+        return P, logL, status, niter
+
+    def maximize(self, p0, **kw):
+        """`maximize_batch` for one parameter vector: (p, logL, status, niter)."""
+        self._check_scalar(p0)
+        P, logL, status, niter = self.maximize_batch(np.asarray(p0, dtype=float).reshape(1, -1), **kw)
+        return P[0], float(logL[0]), int(status[0]), int(niter[0])
 
     def loglike_hvp_batch(self, P, V, out=None):
         """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's
