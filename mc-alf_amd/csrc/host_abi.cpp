@@ -291,6 +291,9 @@ static int create_impl(const mcalf_spec* sp, mcalf_ctx* ctx) {
         }
     }
     ctx->dnu_seg = dnu_seg;
+    // The set-up finds a record's segment-mask word by boundary search where the ends of the tile's real segments form a
+    // monotone sequence (established here, once; a wavelength array out of order keeps the walk over all 64 segments).
+    ctx->seg_search = (ctx->selfhalo && seg_ends_searchable(nu.data(), ctx->npix, &ctx->seg_nreal)) ? 1 : 0;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_segok.p, segok.size() * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMemcpy(ctx->d_segok, segok.data(), segok.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_wtab.p, sizeof(VT_INTERP_W_HOST)));

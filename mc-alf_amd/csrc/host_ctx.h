@@ -175,6 +175,7 @@ struct mcalf_ctx {
     DevBuf<LineDev> d_lines;
     DevBuf<unsigned long long> d_segok;
     double dnu_seg = 0;
+    int seg_nreal = 0, seg_search = 0;  // single-tile contexts: real segments, and whether the set-up may search their ends (kernel_args.h)
     // workspaces (grown on demand)
     DevBuf<double> d_P, d_out, d_partial, d_model, d_bounds, d_prior, d_recs, d_taps;
     DevBuf<SampleHdr> d_hdr;

@@ -36,7 +36,7 @@ KArgs make_kargs(const mcalf_ctx* ctx, const LaunchReq& q, int64_t row0, int64_t
     a.startind = ctx->startind; a.endind = ctx->endind;
     a.freespecres = ctx->freespecres; a.freecont = ctx->freecont;
     a.targonly = q.targonly; a.mode = mode; a.jax_half = ctx->jax_half; a.onecomp_fill = q.onecomp_fill;
-    a.selfhalo = ctx->selfhalo;
+    a.selfhalo = ctx->selfhalo; a.seg_search = ctx->seg_search ? ctx->seg_nreal : 0;
     a.specres_fixed = ctx->specres_fixed; a.contval_fixed = ctx->contval_fixed; a.velstep = ctx->velstep;
     a.log2pi = std::log(2.0 * M_PI);
     a.prior_lo = q.from_cube ? ctx->d_prior : nullptr;

@@ -4,6 +4,7 @@
 // host files are compiled without the HIP language mode.  Part of the kernel-source hash (mc-alf_amd/build.py): a
 // change of a layout here changes what the device code does.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -96,6 +97,11 @@ struct KArgs {
     int prior_int;          // 1: int() on the ncomp slot (_scale_cube_pc), 0: leave (_scale_cube_mn)
     // persistent fused kernel: work items (live point x tile) of this launch and its item queue
     int nitems, persist;
+    // Segment-mask words of single-tile contexts (the end of this file), wave-uniform: > 0 = the tile's real segments
+    // (ceil(npix / 64), the virtually continued last one included), whose end frequencies mcalf_create found monotone -- the
+    // set-up finds a record's word by boundary search; 0 = the walk over all 64 segments.  (In the padding in front of
+    // `queue`: the layout, and with it the fused kernels' machine code, is the one without it.)
+    int seg_search;
     unsigned int* queue;    // reset to 0 by the set-up kernel of the same launch
     // Hand-out order of the persistent kernel (single-tile spectra): ticket t of the queue is live point
     // order[t] -- the live points sorted by their component count, longest first (written by one extra workgroup
@@ -214,5 +220,103 @@ constexpr int kWideTapChunk = 512;                         // taps staged in LDS
 MCALF_INTERNAL const void* wide_taps_kernel_ptr(bool jax);             // (const KArgs a, double* taps, long tap_stride, SampleHdr* hdr), grid = rows
 MCALF_INTERNAL const void* wide_conv_kernel_ptr(bool jax);             // (const KArgs a, const double* flux, const double* taps, long tap_stride, const SampleHdr* hdr, int nblocks), grid = (ceil(npix / kWideBlockPix), rows)
 MCALF_INTERNAL const void* wide_rows_kernel_ptr();             // (const double* rows, double* out, long batch): (R, cont, N, z, b) rows with cont := 1
+
+// ---- segment-mask words of single-tile contexts -----------------------------------------------------------------------
+// Which of a tile's 64 segments (64 pixels each) a line's far wing is interpolated on.  Plain C++ that compiles for the host
+// and for the device from ONE source: the set-up (kernels.hip, setup_sample) forms the words with it, mcalf_create checks
+// the search's precondition with it, and tests/stubs/segment_search_check.cpp compares search and walk word for word on
+// the CPU.
+//
+// A segment is interpolated for a line (A, B, uthr) when both of its end pixels have u >= uthr, or both u <= -uthr, with
+// u = fma(nu, A, -B) -- the fused kernel's own expression and its own four comparisons (eval_line) -- and the context allows
+// it (segok).  The WALK evaluates that at all 128 ends.  The SEARCH uses that fl(nu A - B) is monotone in nu for fixed A and
+// B, whatever the sign of A (rounding is monotone): along a monotone sequence of end frequencies each of the predicates
+// u >= uthr and u <= -uthr holds on a prefix or on a suffix, so two evaluations at the outer ends and a bisection between
+// them find where its run begins or ends -- the same fma and comparisons at actual end frequencies, only fewer of them:
+// 2 + 2 (floor(log2(2 nreal - 1)) + 1) <= 16 instead of 128.  u is NaN at one end exactly when it is at all of them (NaN in A or
+// B, or inf - inf: none depends on nu as long as every nu is finite and positive), and then no predicate holds anywhere.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MCALF_HD __host__ __device__ __forceinline__
+#else
+#define MCALF_HD inline
+#endif
+
+constexpr int kSegs = 64;               // segments of a tile
+constexpr int kSegEnds = 2 * kSegs;     // end table: entry 2 m = first pixel frequency of segment m, 2 m + 1 = its last
+
+// Index into nu[] of entry k of the end table.
+MCALF_HD int seg_end_pixel(int k) { return 64 * (k >> 1) + 63 * (k & 1); }
+
+MCALF_HD double seg_u(double nu, double A, double B) { return std::fma(nu, A, -B); }
+MCALF_HD bool seg_above(double u, double uthr) { return u >= uthr; }
+MCALF_HD bool seg_below(double u, double uthr) { return u <= -uthr; }
+
+// Bit m = segment m  ->  bit 8 i + v = segment 8 v + i (the layout of the records' words: byte i belongs to the wave that
+// evaluates the pixels of segments i, i + 8, ..): the transpose of the 8 x 8 bit matrix.
+MCALF_HD uint64_t seg_transpose(uint64_t x) {
+    uint64_t t;
+    t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;  x ^= t ^ (t << 7);
+    t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull; x ^= t ^ (t << 14);
+    t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull; x ^= t ^ (t << 28);
+    return x;
+}
+
+// The walk: every segment, both ends.  `ends` has kSegEnds entries, `ok` bit m = segment m may be interpolated.
+MCALF_HD uint64_t seg_word_walk(double A, double B, double uthr, const double* ends, uint64_t ok) {
+    uint64_t w = 0;
+    for (int m = 0; m < kSegs; ++m) {
+        const double u0 = seg_u(ends[2 * m], A, B), u1 = seg_u(ends[2 * m + 1], A, B);
+        const bool in = (seg_above(u0, uthr) && seg_above(u1, uthr)) || (seg_below(u0, uthr) && seg_below(u1, uthr));
+        if (in && ((ok >> m) & 1ull)) w |= 1ull << (8 * (m & 7) + (m >> 3));      // (placed by the layout's definition, not by seg_transpose)
+    }
+    return w;
+}
+
+// The search.  Precondition (seg_ends_searchable): ends[0 .. 2 nreal) finite, positive and monotone, the segments from
+// nreal on wholly virtual (nu = 0 at both ends: ONE classification, evaluated with the same fma at nu = 0).
+MCALF_HD uint64_t seg_word_search(double A, double B, double uthr, const double* ends, int nreal, uint64_t ok) {
+    const int last = 2 * nreal - 1;
+    const double uF = seg_u(ends[0], A, B), uV = seg_u(0.0, A, B);
+    const bool aF = seg_above(uF, uthr), bF = seg_below(uF, uthr);
+    // aPos / bPos: the last end at which the predicate still has the value it has at end 0 (`last`: it never changes), by
+    // steps of falling powers of two from the largest one <= last (the same for every record of the context); a step past
+    // the last end looks at the last end.  Both predicates in one loop, so that their two loads are in flight together.
+    int aPos = 0, bPos = 0;
+    for (int step = 1 << (31 - __builtin_clz((unsigned)last)); step > 0; step >>= 1) {
+        const int ai = aPos + step < last ? aPos + step : last, bi = bPos + step < last ? bPos + step : last;
+        if (seg_above(seg_u(ends[ai], A, B), uthr) == aF) aPos = ai;
+        if (seg_below(seg_u(ends[bi], A, B), uthr) == bF) bPos = bi;
+    }
+    // A predicate true at end 0 holds at the ends [0, pos + 1): on the segments [0, (pos + 1) / 2) with both ends.  One false
+    // at end 0 holds at the ends [pos + 1, 2 nreal): on the real segments from (pos + 2) / 2 on.  n <= 64: shifted in two halves.
+    const int aN = (aPos + (aF ? 1 : 2)) >> 1, bN = (bPos + (bF ? 1 : 2)) >> 1;
+    const uint64_t aFrom = (~0ull << (aN >> 1)) << (aN - (aN >> 1)), bFrom = (~0ull << (bN >> 1)) << (bN - (bN >> 1));   // bits n ..
+    const uint64_t real = ~((~0ull << (nreal >> 1)) << (nreal - (nreal >> 1)));
+    uint64_t w = ((aF ? ~aFrom : aFrom) | (bF ? ~bFrom : bFrom)) & real;
+    if (seg_above(uV, uthr) || seg_below(uV, uthr)) w |= ~real;
+    return seg_transpose(w & ok);
+}
+
+// Host, once per context: may the records of a spectrum with this pixel-frequency table (4096 entries, nu[i] of the
+// real and the virtually continued pixels, 0 beyond) take the search?  The ends of the nreal = ceil(npix / 64) real
+// segments must be finite, positive and monotone -- equal neighbours allowed, either direction -- and every later end 0.
+inline bool seg_ends_searchable(const double* nu, long npix, int* nreal_out) {
+    const int nreal = (int)((npix + 63) / 64);
+    if (nreal_out) *nreal_out = nreal;
+    if (npix < 1 || nreal > kSegs) return false;
+    bool up = true, down = true;
+    for (int k = 0; k < 2 * nreal; ++k) {
+        const double v = nu[seg_end_pixel(k)];
+        if (!std::isfinite(v) || !(v > 0.0)) return false;
+        if (k > 0) {
+            const double p = nu[seg_end_pixel(k - 1)];
+            if (v < p) up = false;
+            if (v > p) down = false;
+        }
+    }
+    for (int k = 2 * nreal; k < kSegEnds; ++k)
+        if (nu[seg_end_pixel(k)] != 0.0) return false;
+    return up || down;
+}
 
 }  // namespace mcalf

@@ -390,28 +390,45 @@ __device__ __forceinline__ double segment_masks(const double (&rec)[kRecStride],
     for (unsigned long long todo = have; todo != 0; todo &= todo - 1) {       // (wave-uniform)
         const int r = __builtin_ctzll(todo);
         const double A = readlane_f64(rec[0], r), B = readlane_f64(rec[1], r), uthr = readlane_f64(rec[7], r);
-        const double u0 = fma(nuLo, A, -B), u1 = fma(nuHi, A, -B);
-        const unsigned long long mp = __builtin_amdgcn_ballot_w64(u0 >= uthr) & __builtin_amdgcn_ballot_w64(u1 >= uthr);
-        const unsigned long long mn = __builtin_amdgcn_ballot_w64(u0 <= -uthr) & __builtin_amdgcn_ballot_w64(u1 <= -uthr);
+        const double u0 = seg_u(nuLo, A, B), u1 = seg_u(nuHi, A, B);
+        const unsigned long long mp = __builtin_amdgcn_ballot_w64(seg_above(u0, uthr)) & __builtin_amdgcn_ballot_w64(seg_above(u1, uthr));
+        const unsigned long long mn = __builtin_amdgcn_ballot_w64(seg_below(u0, uthr)) & __builtin_amdgcn_ballot_w64(seg_below(u1, uthr));
         const unsigned long long w = (mp | mn) & okW;
         if (lane == r) word = w;
     }
     return __builtin_bit_cast(double, word);
 }
 
+// A wave's table of segment-end frequencies in LDS (kSegEnds doubles of its own: entry 2 m / 2 m + 1 = first / last pixel
+// frequency of segment m), which the records' searches then read lane by lane (seg_word_search) -- two loads a lane, the
+// same two the walk needs.  Written and read by the one wave: no workgroup barrier.  All 64 lanes must be active.
+__device__ __forceinline__ void fill_segment_ends(const KArgs& a, int lane, double* ends) {
+    static_assert(kSegEnds == 128, "two ends per lane");
+    const double e0 = a.nu[seg_end_pixel(lane)], e1 = a.nu[seg_end_pixel(lane + 64)];
+    ends[lane] = e0; ends[lane + 64] = e1;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // segMasks: the records carry their segment-mask word in slot 7 instead of the threshold (the set-up kernel and the
 // streaming set-up phase of single-tile contexts, whose fused kernel is eval_line<true>); the one-launch variant, the
-// resident kernel and tiled contexts leave the threshold there and compute nothing more.
+// resident kernel and tiled contexts leave the threshold there and compute nothing more.  `ends` is then the wave's table
+// of segment ends (fill_segment_ends).  Every lane finds the word of ITS record by boundary search (seg_word_search: the
+// same fma and comparisons at 16 of the 128 ends) where mcalf_create found the context's ends monotone (a.seg_search,
+// wave-uniform); otherwise the walk over all of them stays in force (segment_masks).
 template <bool kZeroPad>
 __device__ __forceinline__ void setup_sample(const KArgs& a, long s, int lane, double* recs, double* taps, bool writeTaps,
-                                             SampleHdr* hdrOut, bool writeTheta, bool segMasks) {
+                                             SampleHdr* hdrOut, bool writeTheta, bool segMasks, const double* ends = nullptr) {
     const int rowlen = (a.mode == kModeOneComp) ? 5 : a.ndim;
     const double* p = a.P + (size_t)s * rowlen;
-    // (segment masks: this lane's two pixel frequencies and the tile's interpolable segments go out with the row's loads)
+    const bool walk = segMasks && a.seg_search == 0;
+    // (the walk: lane l tests segment mseg of one record at a time)
     const int mseg = 8 * (lane & 7) + (lane >> 3);
     double nuLo = 0.0, nuHi = 0.0;
     unsigned long long tileOk = 0;
-    if (segMasks) { nuLo = a.nu[64 * mseg]; nuHi = a.nu[64 * mseg + 63]; tileOk = a.segok[0]; }
+    if (segMasks) tileOk = a.segok[0];
+    if (walk) { nuLo = ends[2 * mseg]; nuHi = ends[2 * mseg + 1]; }
     // ---- 1. decode the parameter vector ---------------------------------------------------
     double R, cont;
     int nc, nfill_eff;
@@ -440,10 +457,10 @@ __device__ __forceinline__ void setup_sample(const KArgs& a, long s, int lane, d
     const int nTargetSlots = (a.mode == kModeOneComp) ? nl_eff : a.ncompmax * a.nlines;
     const int nSlots = nTargetSlots + ((a.mode == kModeOneComp) ? 0 : a.nfill);
     int ngenLane = 0;
-    // (segment masks: whole rounds of 64 -- the lanes past the last slot repeat it, write nothing and serve the ballots)
-    const int nSlotsRun = segMasks ? (nSlots + 63) & ~63 : nSlots;
+    // (the walk: whole rounds of 64 -- the lanes past the last slot repeat it, write nothing and serve the ballots)
+    const int nSlotsRun = walk ? (nSlots + 63) & ~63 : nSlots;
     for (int slot0 = lane; slot0 < nSlotsRun; slot0 += 64) {
-        const bool spare = segMasks && slot0 >= nSlots;
+        const bool spare = walk && slot0 >= nSlots;
         const int slot = spare ? nSlots - 1 : slot0;
         double logN, z, b;
         const LineDev* ln;
@@ -470,9 +487,11 @@ __device__ __forceinline__ void setup_sample(const KArgs& a, long s, int lane, d
         if (spare) dst = -1;
         double rec[kRecStride];
         build_line_record(rec, logN, z, b, *ln, a.dnu_seg);
-        if (segMasks)
+        if (walk)
             rec[7] = segment_masks(rec, lane, __builtin_amdgcn_ballot_w64(dst >= 0), nuLo, nuHi,
                                    __builtin_amdgcn_ballot_w64(((tileOk >> mseg) & 1ULL) != 0));
+        else if (segMasks)
+            rec[7] = __builtin_bit_cast(double, (unsigned long long)seg_word_search(rec[0], rec[1], rec[7], ends, a.seg_search, tileOk));
         ngenLane += __popcll(__ballot(dst >= 0 && rec[6] != 0.0));        // (wave-uniform count)
         if (dst >= 0) {
 #pragma unroll
@@ -620,9 +639,12 @@ __global__ __launch_bounds__(kSetupBlockMax) void mcalf_sample_kernel(const KArg
     if (s >= batch) return;
     const int lane = threadIdx.x & 63;
     if (s == 0 && lane == 0) *a.queue = 0u;          // item queue of the fused kernel that follows on the stream
+    __shared__ double sEnds[kSetupBlockMax / 64][kSegEnds];
+    double* ends = sEnds[threadIdx.x >> 6];
+    if (a.selfhalo) fill_segment_ends(a, lane, ends);
     setup_sample<kZeroPad>(a, s, lane, a.recs + (size_t)s * a.ncl_cap * kRecStride,
                            a.taps + (a.taps_shared ? 0 : (size_t)s * (2 * a.n_cap + 8)), !a.taps_shared || s == 0, a.hdr + s, true,
-                           a.selfhalo != 0);
+                           a.selfhalo != 0, ends);
 }
 
 // Lines outside the fast path's damping range (flag != 0; none for physical resonance lines).  Kept out
@@ -654,6 +676,9 @@ __device__ __forceinline__ void eval_general_lines(const double* __restrict__ sR
 template <bool kZeroPad, bool kSelfHalo>
 __device__ __forceinline__ void stream_setup_phase(const KArgs& a, int tid, int x, int* sClaim) {
     const int lane = tid & 63, wave = tid >> 6;
+    // (the wave's table of segment ends, once for all its rows: behind the claim words, in LDS the item loop lays out afresh)
+    double* ends = reinterpret_cast<double*>(sClaim) + 16 + wave * kSegEnds;
+    if (kSelfHalo) fill_segment_ends(a, lane, ends);
     constexpr int nx = kXcds;
     const int nloc = stream_rows_of(a.nrows, x, nx), nblk = (nloc + 7) >> 3;      // this XCD's live points / local blocks
     const int eager = min(a.eager_rows, nblk);
@@ -713,7 +738,7 @@ __device__ __forceinline__ void stream_setup_phase(const KArgs& a, int tid, int 
             SampleHdr* hdrp = reinterpret_cast<SampleHdr*>(reinterpret_cast<double*>(a.hdr) + (size_t)r * a.hdr_stride);
             if (ok) {
                 setup_sample<kZeroPad>(as, (long)r, lane, a.recs + (size_t)r * a.rec_stride, a.taps + (size_t)r * a.tap_stride, true, hdrp, true,
-                                       kSelfHalo);
+                                       kSelfHalo, ends);
             } else if (lane == 0) {                      // gave up on the host: a row nobody will mistake for a result
                 SampleHdr h;
                 h.cont = 0.0; h.bot = 1.0; h.ncl = 0; h.n = 0; h.bad = 1; h.ngeneral = 0;
