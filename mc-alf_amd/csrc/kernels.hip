@@ -798,9 +798,22 @@ struct ItemLoads {
     SampleHdr hd;
 };
 
-// Issue every global load of work item w (one memory round trip; the record and tap copies run to their
-// provisioned sizes, which do not depend on the header: slots beyond the sample's own counts hold stale
-// values that are never read).
+// The eight node offsets of a segment, a byte each (byte k = VT_INTERP_NODES[k]): a lane forms the offset of its node by
+// a shift and a mask.  Indexed by the lane, the table is a global load, and the node's own load waits for its answer.
+constexpr unsigned long long interp_node_word() {
+    unsigned long long v = 0;
+    for (int k = 0; k < VT_INODES; ++k) v |= (unsigned long long)VT_INTERP_NODES[k] << (8 * k);
+    return v;
+}
+constexpr unsigned long long kNodeWord = interp_node_word();
+static_assert(VT_INODES == 8 && kNodeWord == 0x3F3C3327180C0300ULL, "node offsets 0, 3, 12, 24, 39, 51, 60, 63: one byte each");
+__device__ __forceinline__ int interp_node(int k) { return (int)((kNodeWord >> (8 * (k & 7))) & 0xFFu); }
+
+// Issue every global load of work item w: no load's address depends on another load's answer, and nothing here reads
+// a loaded value, so no wait sits between the first load and the last -- they are drained in one place, at the top of the
+// item that uses them (the header's counts, wave-uniform, stay in vector registers until then: see fused_items).  The
+// record and tap copies run to their provisioned sizes, which do not depend on the header: slots beyond the sample's own
+// counts hold stale values that are never read.
 // kCoh: the streaming launch -- header, records and taps of a live point were written by a wave of the SAME launch on the
 // same XCD, into rows of their own 128-byte lines (a.hdr_stride / rec_stride / tap_stride); see stream_setup_phase.
 template <bool kZeroPad, bool selfHalo, bool kInline, bool kCoh = false>
@@ -812,13 +825,11 @@ __device__ __forceinline__ void request_item(const KArgs& a, int w, int tid, Ite
     constexpr int kTRegs = (VT_NY * VT_NTOT + kBlock - 1) / kBlock;
     constexpr int kRecRegs = 2;
     const int recTotal = a.ncl_cap * kRecStride, tapTotal = 2 * a.n_cap + 8;
-    const int s = w / a.ntiles;
-    const int tileIdx = w - s * a.ntiles;
+    const int s = selfHalo ? w : w / a.ntiles;           // (self-halo: a spectrum of ONE tile -- no division)
+    const int tileIdx = selfHalo ? 0 : w - s * a.ntiles;
+    // (no test around the load: a slice past the table's end re-reads its last entry and is never stored)
 #pragma unroll
-    for (int i = 0; i < kTRegs; ++i) {
-        const int idx = tid + i * kBlock;
-        L.treg[i] = (idx < VT_NY * VT_NTOT) ? a.tabs[idx] : 0.0;
-    }
+    for (int i = 0; i < kTRegs; ++i) L.treg[i] = a.tabs[min(tid + i * kBlock, VT_NY * VT_NTOT - 1)];
     if (!kInline) {                                      // (one-launch variant: the workgroup sets the live point up itself)
         // (plain, cached loads in both cases.  Streaming launch: the row was set up by a wave of THIS XCD -- its L2 holds
         // what was written -- and owns its 128-byte lines, so this CU's L1 has not seen them before)
@@ -826,8 +837,8 @@ __device__ __forceinline__ void request_item(const KArgs& a, int w, int tid, Ite
         const double* gt = a.taps + (kCoh ? (size_t)s * a.tap_stride : (a.taps_shared ? 0 : (size_t)s * tapTotal));
         L.hd = kCoh ? *reinterpret_cast<const SampleHdr*>(reinterpret_cast<const double*>(a.hdr) + (size_t)s * a.hdr_stride) : a.hdr[s];
 #pragma unroll
-        for (int i = 0; i < kRecRegs; ++i) L.rreg[i] = (tid + i * kBlock < recTotal) ? gr[tid + i * kBlock] : 0.0;
-        L.tapreg = (tid < tapTotal) ? gt[tid] : 0.0;
+        for (int i = 0; i < kRecRegs; ++i) L.rreg[i] = gr[min(tid + i * kBlock, recTotal - 1)];   // (as the T slices: no test)
+        L.tapreg = gt[min(tid, tapTotal - 1)];
     }
     const int t0 = tileIdx * a.tile;
     const int ext0 = selfHalo ? 0 : t0 - a.n_cap;
@@ -851,10 +862,10 @@ __device__ __forceinline__ void request_item(const KArgs& a, int w, int tid, Ite
         // segment masks from the set-up (eval_line<true>): the wave holds the nodes of the ADJACENT segments 8 wv .. 8 wv + 7,
         // and which of them are interpolated comes with each line
         const int wv = tid >> 6, ln = tid & 63;
-        L.nuNode = a.nu[kBlock * wv + 64 * (ln >> 3) + VT_INTERP_NODES[ln & 7]];
+        L.nuNode = a.nu[kBlock * wv + 64 * (ln >> 3) + interp_node(ln)];
     } else if (kFarInterp) {
         const int wv = tid >> 6, ln = tid & 63;
-        int e = ext0 + 64 * wv + kBlock * (ln >> 3) + VT_INTERP_NODES[ln & 7];
+        int e = ext0 + 64 * wv + kBlock * (ln >> 3) + interp_node(ln);
         if (!selfHalo && (e < 0 || e >= a.npix)) { e %= npixW; if (e < 0) e += npixW; }   // such segments are never interpolated
         L.nuNode = a.nu[e];
         L.tileMask = a.segok[tileIdx];                                         // bit m = segment m = wave + 8 j
@@ -943,8 +954,8 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
         const bool hasCoef = tid < VT_NTOT;
         const int coefPos = tid + (tid >= VT_Z0_OFF ? 1 : 0) + (tid >= VT_ZF_OFF ? 1 : 0);
         const bool coreCoef = tid < VT_NCORE;
-        const int s = w / a.ntiles;
-        const int tileIdx = w - s * a.ntiles;
+        const int s = selfHalo ? w : w / a.ntiles;         // (self-halo: a spectrum of ONE tile -- no division)
+        const int tileIdx = selfHalo ? 0 : w - s * a.ntiles;
         // ---- 1. per-sample set-up comes from mcalf_sample_kernel: header, records, taps -----------------
         // The tile always carries the full provisioned halo n_cap (so that its 64-pixel segments are the
         // same for every sample); a sample with a shorter kernel simply starts `shift` entries in.
@@ -969,7 +980,7 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
             tau[j] = (zero && idx < extCount) ? INFINITY : 0.0;  // exp(-inf) = 0
         }
         // far-wing interpolation state: this lane's node pixel, the wave's interpolable segments
-        const double nuNode = L.nuNode;
+        double nuNode = L.nuNode;
         double farNode = 0.0;
         unsigned long long segOk = 0;
         if (kFarInterp && !kPreMask) {                    // (kPreMask: the mask words have it folded in)
@@ -986,6 +997,15 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
             if (tid < 64) setup_sample<kZeroPad>(a, s, tid, sRec, sW, true, sHdr, tileIdx == 0, false);
         } else {
             hd = L.hd;
+            // The header's counts are the same in every lane, and the compiler knows it: left alone it reads them back into
+            // scalar registers right behind the load -- every wave then waits in request_item for a full memory round
+            // trip, with the record, tap and frequency loads not yet issued.  Through an empty asm they stay vector
+            // values up to here, the top of the item that uses them, where the loads are drained anyway.
+            asm volatile("" : "+v"(hd.ncl), "+v"(hd.n), "+v"(hd.bad), "+v"(hd.ngeneral));
+            hd.ncl = __builtin_amdgcn_readfirstlane(hd.ncl);
+            hd.n = __builtin_amdgcn_readfirstlane(hd.n);
+            hd.bad = __builtin_amdgcn_readfirstlane(hd.bad);
+            hd.ngeneral = __builtin_amdgcn_readfirstlane(hd.ngeneral);
 #pragma unroll
             for (int i = 0; i < kRecRegs; ++i)
                 if (tid + i * kBlock < recTotal) sRec[tid + i * kBlock] = L.rreg[i];
@@ -1004,23 +1024,51 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
             const int idx = tid + i * kBlock;
             if (idx < VT_NY * VT_NTOT) sT[idx] = L.treg[i];
         }
-        // the item after this one: the first comes from the grid, the rest from the queue
         // Ticket of the item after this one: the first comes from the grid, the rest from the queue.  With an
         // ordered hand-out (single-tile instantiations) the ticket still has to be looked up in a.order -- a second
-        // dependent memory round trip -- so thread 0 keeps both in registers and publishes them behind the
-        // component loop, where they have long arrived; otherwise the ticket is published at once.
-        int tHeld = nItems, wHeld = 0;
-        unsigned stHeld = 0u;
-        if (tid == 0) {
-            tHeld = a.persist ? firstTickets + (int)atomicAdd(queue, 1u) : nItems;
-            if (kOrdered) wHeld = (tHeld < nItems) ? item_of(tHeld) : 0;
-            else if (kStream) {
-                // (streaming launch: thread 0 also takes a first look at the next row's stamp -- the answer lands while
-                // the component loop runs and travels to the workgroup with the ticket)
-                wHeld = (tHeld < nItems) ? item_of(tHeld) : 0;
-                if (tHeld < nItems) stHeld = __hip_atomic_load(a.ready + wHeld / a.ntiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else { sNext[0] = tHeld; sNext[1] = tHeld; }
+        // memory round trip that depends on the first.  Only the atomic is issued here: wave 0 reaches the item's first
+        // barrier without waiting for its answer.  The look-up follows behind the component loop (resolve_ticket): the
+        // ticket goes to sNext there -- nobody has read sNext since the barrier behind the previous item's publish, and
+        // nobody will before this item's -- and the item it stands for is published behind the node interpolation and
+        // the exponentials, which cover its way from memory; thread 0 holds ONE value at a time through the loop.
+        // The tiled batch instantiations publish the ticket at once.
+        int wHeld = 0;
+        unsigned stHeld = 0u, tRaw = 0u;
+        if (kDeferTicket) {
+            // The frequencies are waited for HERE, with everything else request_item loaded: answers come back in the
+            // order of issue and are counted that way, so a wait for a frequency behind the atomic -- in the first line
+            // of the component loop -- would be a wait for the atomic's answer too.
+            asm volatile("" : "+v"(nuNode));
+#pragma unroll
+            for (int j = 0; j < kPpt; ++j) asm volatile("" : "+v"(nu[j]));
         }
+        if (tid == 0) {
+            if (kDeferTicket) {
+                // (the queue is addressed through an offset of 0 that the compiler takes for a per-lane value.  For an
+                // atomic on a wave-uniform address it counts the active lanes, lets one lane add the count and hands
+                // every lane its share behind a wait for the answer, right here -- for the one lane that takes a ticket)
+                int qoff = 0;
+                asm volatile("" : "+v"(qoff));
+                if (a.persist) tRaw = atomicAdd(queue + qoff, 1u);
+            } else {
+                const int tHeld = a.persist ? firstTickets + (int)atomicAdd(queue, 1u) : nItems;
+                sNext[0] = tHeld; sNext[1] = tHeld;
+            }
+        }
+        auto resolve_ticket = [&]() {
+            // (the first use of the atomic's answer stays here -- in EVERY wave: the wait for it then stands ahead of the
+            // branch, where it costs the other waves nothing; inside, they would meet it where the register is next
+            // written, behind the look-up's load, which the in-order counter would make wave 0 wait for as well)
+            asm volatile("" : "+v"(tRaw));
+            if (tid == 0) {
+                const int tHeld = a.persist ? firstTickets + (int)tRaw : nItems;
+                sNext[0] = tHeld;
+                wHeld = (tHeld < nItems) ? item_of(tHeld) : 0;
+                // (streaming launch: thread 0 also takes a first look at the next row's stamp -- the answer lands while
+                // the rest of the component loop runs and travels to the workgroup with the ticket)
+                if (kStream && tHeld < nItems) stHeld = __hip_atomic_load(a.ready + wHeld / a.ntiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        };
 
         // ---- 2. tau for this thread's pixels ----------------------------------------------------
         __syncthreads();                                   // publishes sRec, sW, sT, sNext (and the header of the one-launch variant)
@@ -1093,6 +1141,9 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
         }
         if (hd.ngeneral > 0 && ncl_run > 0) eval_general_lines(sRec, ncl, nu, tau);
         __builtin_amdgcn_s_setprio(0);
+        // (behind the loop, not inside it: a loop that loads from memory and reads a register loaded ahead of it gets a
+        // full drain in front of its first iteration -- wave 0 would wait for the atomic right behind the first barrier)
+        if (kDeferTicket) resolve_ticket();
         // Interpolate the far-wing node sums to the pixels (tau[j] += sum_k W[lane][k] F[segment j][node k]),
         // then flux = exp(-tau) into the LDS tile.  The node sums travel through the (now dead) folded-table
         // region, one 64-entry row per wave; the tile holds only the sample's own halo n (<= n_cap).
@@ -1162,7 +1213,7 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
             asm volatile("" : "+v"(zero));                 // formed here: hoisted out of the item loop it was spilled
             sF[tile_pos(extTight + tid)] = zero;
         }
-        if (kDeferTicket && tid == 0) { sNext[0] = tHeld; sNext[1] = wHeld; if (kStream) sNext[2] = (int)stHeld; }
+        if (kDeferTicket && tid == 0) { sNext[1] = wHeld; if (kStream) sNext[2] = (int)stHeld; }   // (sNext[0]: resolve_ticket)
         __syncthreads();
         if (kDeferTicket) {
             tNext = __builtin_amdgcn_readfirstlane(sNext[0]);

@@ -191,7 +191,7 @@ def main(out_path):
     L.append("// Far-wing interpolation over a 64-pixel segment: 8 nodes (pixel positions) and the Lagrange")
     L.append("// weights W[p][k] in pixel-index space (DESIGN.md, 'far-wing interpolation').")
     L.append("#define VT_INODES 8")
-    L.append("static const int VT_INTERP_NODES[8] = {" + ", ".join(str(v) for v in INTERP_NODES) + "};")
+    L.append("static constexpr int VT_INTERP_NODES[8] = {" + ", ".join(str(v) for v in INTERP_NODES) + "};")
     L.append("static const double VT_INTERP_W_HOST[64 * 8] = {")
     for row in interp_weights():
         L.append("  " + ", ".join(repr(float(v)) for v in row) + ",")
