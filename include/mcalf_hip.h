@@ -84,7 +84,9 @@ extern "C" {
                                     mcalf_model_band_batch[_device], per-pixel mean, variance and quantiles of the model
                                     over the rows of a chain;
                                     mcalf_fisher_matvec_batch[_device], the Fisher product J^T W J v on the device, and
-                                    mcalf_maximize_batch[_device], batched Levenberg-Marquardt maximisation of logL) */
+                                    mcalf_maximize_batch[_device], batched Levenberg-Marquardt maximisation of logL;
+                                    mcalf_slice_replace_batch[_device], nested sampling's replacement step: batched slice
+                                    moves in the unit cube under a likelihood constraint) */
 
 enum {
     MCALF_OK = 0,
@@ -484,6 +486,54 @@ int mcalf_maximize_batch(mcalf_ctx* ctx, const double* P0, int64_t batch, const 
  * or a larger batch and block size it allocates nothing. */
 int mcalf_maximize_batch_device(mcalf_ctx* ctx, const double* dP0, int64_t batch, const mcalf_fit_opts* opts, double* dP, double* dlogL,
                                 int32_t* dstatus, int32_t* dniter, void* stream);
+
+/* Nested sampling's replacement step: every row of U0 (batch x ndim, a point of the unit cube of mcalf_set_prior's box --
+ * MCALF_ERR_INVALID if none is set) is a chain that makes nmoves slice-sampling moves under the hard constraint
+ * logL > Lmin[row], logL being exactly mcalf_loglike_cube_batch's value.  D (ndirs x ndim, row-major) holds the direction
+ * rows, shared by all rows of the call; sid[row] is the row's random stream (the caller makes them distinct).  Rows run in
+ * lock step, one trial per row and step:
+ *   start    logL(U0) by one cube launch.  A row whose start has an entry outside [0, 1] or a NaN, or for which
+ *            logL(U0) > Lmin is false (a NaN logL makes it false; Lmin = -inf passes every finite logL and +inf), has status -1
+ *            and is returned as given, with logL = logL(U0).
+ *   step it = 1 .. max_steps, for a row with x its point, (w0, w1, w2, w3) = Philox4x64-10 of counter (it, 0, sid, 0) and key
+ *   (seed, 0) (multipliers 0xD2E7470EE14C6C93, 0xCA5A826395121157, Weyl constants 0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B --
+ *   numpy's Philox(counter=[0, 0, sid, 0], key=[seed, 0]) returns exactly these blocks; w2 and w3 are reserved):
+ *     decide   (from the second step on) the trial y of the step before is accepted iff logL(y) > Lmin: x <- y, logL <- logL(y),
+ *              moves + 1, and the row needs a new direction; at moves == nmoves the row is finished, status 1.  Rejected:
+ *              tl <- t if t < 0, else tr <- t.
+ *     propose  a row that needs a direction takes d = D[w0 mod ndirs] and the chord of its line through the cube:
+ *              tl = max_k min(a_k, b_k), tr = min_k max(a_k, b_k) over the k with d_k != 0, a_k = (0 - x_k) / d_k,
+ *              b_k = (1 - x_k) / d_k; tl = tr = 0 if d is all zero.  Then xi = (w1 >> 11) 2^-53, t = tl + (tr - tl) xi and
+ *              y_k = x_k + t d_k clamped into [0, 1] (y < 0 ? 0 : (y > 1 ? 1 : y)); nevals + 1.
+ *   Every product, quotient, sum and difference above is ONE correctly rounded IEEE operation (nothing is contracted to an
+ *   FMA), so a trajectory can be restated exactly on the host.  The point sits at t = 0, inside every bracket: a move always ends.
+ * status 0: max_steps steps were run; the row holds its last accepted point, which satisfies the constraint.  A finished row is
+ * carried unchanged (its trial row is its own point, its nevals stops).  On return logL[i] is mcalf_loglike_cube_batch(U)[i] bit
+ * for bit, theta (optional, NULL: not wanted) holds the transformed rows of U as that entry forms them, nevals the trials the row
+ * evaluated (its start not counted) and moves the accepted ones.  A row's results depend on its own (U0 row, Lmin, sid), on D and
+ * on the options alone -- not on its batch, its position or the device count.  A step is one step kernel and one cube logL launch
+ * (set-up kernel + fused kernel) over all rows, finished ones included. */
+typedef struct {
+    int32_t nmoves;          /* accepted moves per row, >= 0 (0: the checked start, status 1 or -1) */
+    int32_t max_steps;       /* lock steps, >= 0 */
+    int32_t ndirs;           /* rows of D, >= 1 */
+    int32_t reserved;
+    uint64_t seed;           /* the Philox key */
+} mcalf_slice_opts;
+/* Host pointers, synchronous: U, theta (batch x ndim), logL, status, nevals, moves (batch each) are outputs; U0 and U must not
+ * overlap.  After every step the call reads the count of rows that proposed a trial (4 bytes) and stops at 0.  A multi-device
+ * context cuts the rows into contiguous blocks as the fit does.  All argument checks (opts or an array NULL, batch < 0, nmoves < 0,
+ * max_steps < 0, ndirs < 1, no prior set, a non-finite entry of D) come before any device work and name the argument.
+ * batch == 0 does nothing. */
+int mcalf_slice_replace_batch(mcalf_ctx* ctx, const double* U0, const double* Lmin, const double* D, const uint64_t* sid, int64_t batch,
+                              const mcalf_slice_opts* opts, double* U, double* theta, double* logL, int32_t* status, int32_t* nevals,
+                              int32_t* moves);
+/* Same, device pointers (opts is a host struct, read during the call; the entries of dD are not checked), on the caller's stream
+ * (single-device contexts).  It runs max_steps steps unconditionally and never synchronises; the bits are the host entry's.
+ * After one call of the same or a larger batch it allocates nothing. */
+int mcalf_slice_replace_batch_device(mcalf_ctx* ctx, const double* dU0, const double* dLmin, const double* dD, const uint64_t* dsid,
+                                     int64_t batch, const mcalf_slice_opts* opts, double* dU, double* dtheta, double* dlogL,
+                                     int32_t* dstatus, int32_t* dnevals, int32_t* dmoves, void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -128,6 +128,19 @@ class mcalf_fit_opts(C.Structure):
     ]
 
 
+class mcalf_slice_opts(C.Structure):
+    _fields_ = [
+        ("nmoves", C.c_int32),
+        ("max_steps", C.c_int32),
+        ("ndirs", C.c_int32),
+        ("reserved", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+# status of a row of mcalf_slice_replace_batch
+MCALF_SLICE_MAXSTEPS, MCALF_SLICE_DONE, MCALF_SLICE_BAD_START = 0, 1, -1
+
 # status of a row of mcalf_maximize_batch
 MCALF_FIT_MAXITER, MCALF_FIT_CONVERGED, MCALF_FIT_ZERO_GRADIENT, MCALF_FIT_LAMBDA, MCALF_FIT_BAD_START = 0, 1, 2, 3, -1
 
@@ -170,6 +183,11 @@ SYMBOLS = {
     "mcalf_maximize_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_maximize_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+    "mcalf_slice_replace_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_slice_replace_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

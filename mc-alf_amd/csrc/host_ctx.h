@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_fit.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -301,6 +301,17 @@ struct mcalf_ctx {
     DevBuf<double> fb[kFbCount];
     DevBuf<int32_t> fit_int, fit_hst;       // (fit_hst: the host-pointer entry's status and niter rows)
     DevBuf<unsigned int> d_fit_live;
+    // The nested-sampling replacement primitive (host_ns.cpp), grown on demand.  The trial rows [batch][ndim] the logL launch
+    // evaluates, their logL [batch], the brackets [3][batch] and the direction index [batch] of one call; the host-pointer
+    // entry's staging (starts, points, constraints, direction rows, logL, transformed rows; stream ids; status, nevals and
+    // moves in ns_hst).  d_ns_live: the counter of rows that proposed a trial, which the host entry reads after every step
+    // through the page-locked word h_ns_live.
+    enum { kNbY, kNbLY, kNbBrk, kNbU0, kNbU, kNbLmin, kNbD, kNbL, kNbTheta, kNbCount };
+    DevBuf<double> nb[kNbCount];
+    DevBuf<int32_t> ns_dir, ns_hst;
+    DevBuf<uint64_t> ns_sid;
+    DevBuf<unsigned int> d_ns_live;
+    PinBuf<unsigned int> h_ns_live;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).

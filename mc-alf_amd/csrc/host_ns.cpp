@@ -1,0 +1,164 @@
+// Host side of the nested-sampling kernels (ns_kernels.hip): the replacement primitive mcalf_slice_replace_batch -- a batch of
+// chains in the unit cube moved by slice sampling under a hard likelihood constraint, in lock step.  A driver over the cube
+// logL launch (host_launch.cpp: launch() with from_cube) -- no Voigt code of its own.  One step is the step kernel (decide on
+// the last trial, propose the next) and one logL launch over the trial rows: the set-up kernel and the fused kernel, as
+// mcalf_loglike_cube_batch_device issues them.
+#include <cmath>
+
+#include "ns_args.h"
+#include "host_ctx.h"
+
+namespace {
+
+struct NsRows {
+    const double *U0, *Lmin, *D; const uint64_t* sid;
+    double *U, *theta, *logL; int32_t *status, *nevals, *moves;
+};
+
+// Everything that is wrong with a call before any device work; `name` is the entry that reports it.  host_d: D is a host array
+// whose entries are read here.
+int ns_check(mcalf_ctx* ctx, const char* name, const NsRows& r, int64_t batch, const mcalf_slice_opts* o, bool host_d) {
+    if (!o) return set_err(ctx, MCALF_ERR_INVALID, "%s: opts is NULL", name);
+    if (batch < 0) return set_err(ctx, MCALF_ERR_INVALID, "%s: batch must be >= 0, got %lld", name, (long long)batch);
+    if (batch > 0 && !r.U0) return set_err(ctx, MCALF_ERR_INVALID, "%s: U0 is NULL", name);
+    if (batch > 0 && !r.Lmin) return set_err(ctx, MCALF_ERR_INVALID, "%s: Lmin is NULL", name);
+    if (batch > 0 && !r.D) return set_err(ctx, MCALF_ERR_INVALID, "%s: D is NULL", name);
+    if (batch > 0 && !r.sid) return set_err(ctx, MCALF_ERR_INVALID, "%s: sid is NULL", name);
+    if (batch > 0 && !r.U) return set_err(ctx, MCALF_ERR_INVALID, "%s: U is NULL", name);
+    if (batch > 0 && !r.logL) return set_err(ctx, MCALF_ERR_INVALID, "%s: logL is NULL", name);
+    if (batch > 0 && !r.status) return set_err(ctx, MCALF_ERR_INVALID, "%s: status is NULL", name);
+    if (batch > 0 && !r.nevals) return set_err(ctx, MCALF_ERR_INVALID, "%s: nevals is NULL", name);
+    if (batch > 0 && !r.moves) return set_err(ctx, MCALF_ERR_INVALID, "%s: moves is NULL", name);
+    if (o->nmoves < 0) return set_err(ctx, MCALF_ERR_INVALID, "%s: nmoves must be >= 0, got %d", name, o->nmoves);
+    if (o->max_steps < 0) return set_err(ctx, MCALF_ERR_INVALID, "%s: max_steps must be >= 0, got %d", name, o->max_steps);
+    if (o->ndirs < 1) return set_err(ctx, MCALF_ERR_INVALID, "%s: ndirs must be >= 1, got %d", name, o->ndirs);
+    if (!ctx) return set_err(ctx, MCALF_ERR_INVALID, "%s: ctx is NULL", name);
+    if (!ctx->prior_set) return set_err(ctx, MCALF_ERR_INVALID, "%s: mcalf_set_prior has not been called (the chains move in its unit cube)", name);
+    if (host_d && batch > 0)
+        for (size_t i = 0, n = (size_t)o->ndirs * (size_t)ctx->ndim; i < n; ++i)
+            if (!std::isfinite(r.D[i]))
+                return set_err(ctx, MCALF_ERR_INVALID, "%s: D has a non-finite entry (row %zu, coordinate %zu: %g)", name, i / ctx->ndim, i % ctx->ndim, r.D[i]);
+    return MCALF_OK;
+}
+
+int launch_ns(mcalf_ctx* ctx, NsKernel k, const NsArgs& a, hipStream_t stream) {
+    void* args[] = {(void*)&a};
+    HIP_TRY(ctx, hipLaunchKernel(ns_kernel_ptr(k), dim3((unsigned)a.nrows), dim3(kNsWave), args, 0, stream));
+    return MCALF_OK;
+}
+
+// logL of the trial rows, exactly what mcalf_loglike_cube_batch_device(Y) writes.
+int trial_logl(mcalf_ctx* ctx, const NsArgs& a, hipStream_t stream) {
+    LaunchReq q(kModeLogL, a.Y, a.nrows, stream);
+    q.d_out = const_cast<double*>(a.LY); q.from_cube = true;
+    return launch(ctx, q);
+}
+
+// The call over `batch` device rows on `stream`.  poll: after every step the host reads the counter of rows that proposed a
+// trial (4 bytes, through a page-locked word) and leaves the loop at 0 -- finished rows are carried, so the rows' bits are those
+// of the unconditional max_steps steps the device entry runs.
+int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o, hipStream_t stream, bool poll) {
+    if (batch <= 0) return MCALF_OK;
+    if (batch > 0x7fff0000LL) return set_err(ctx, MCALF_ERR_RANGE, "batch %lld too large", (long long)batch);
+    const size_t nb = (size_t)batch, ndim = (size_t)ctx->ndim;
+    int rc;
+    if ((rc = grow(ctx, ctx->nb[mcalf_ctx::kNbY], nb * ndim)) || (rc = grow(ctx, ctx->nb[mcalf_ctx::kNbLY], nb)) ||
+        (rc = grow(ctx, ctx->nb[mcalf_ctx::kNbBrk], nb * kNsBrk)) || (rc = grow(ctx, ctx->ns_dir, nb)) || (rc = grow(ctx, ctx->d_ns_live, 1)))
+        return rc;
+    if (poll && !ctx->h_ns_live.p) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_ns_live.p, sizeof(unsigned int), hipHostMallocDefault));
+    NsArgs a = {};
+    a.U0 = r.U0; a.Lmin = r.Lmin; a.D = r.D; a.sid = r.sid; a.U = r.U; a.L = r.logL; a.status = r.status; a.nevals = r.nevals; a.moves = r.moves;
+    a.Y = ctx->nb[mcalf_ctx::kNbY]; a.LY = ctx->nb[mcalf_ctx::kNbLY]; a.brk = ctx->nb[mcalf_ctx::kNbBrk]; a.dir = ctx->ns_dir; a.live = ctx->d_ns_live;
+    a.seed = o.seed; a.nrows = (int)batch; a.ndim = ctx->ndim; a.ndirs = o.ndirs; a.nmoves = o.nmoves;
+    if ((rc = launch_ns(ctx, kNsStart, a, stream)) || (rc = trial_logl(ctx, a, stream)) || (rc = launch_ns(ctx, kNsStarted, a, stream))) return rc;
+    bool open_trial = false;                            // the last trial has been evaluated and not yet decided on
+    for (int it = 1; it <= o.max_steps && o.nmoves > 0; ++it) {
+        if (poll) HIP_TRY(ctx, hipMemsetAsync(a.live, 0, sizeof(unsigned int), stream));
+        a.it = it; a.decide = open_trial ? 1 : 0; a.propose = 1;
+        if ((rc = launch_ns(ctx, kNsStep, a, stream))) return rc;
+        if (poll) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ns_live, a.live, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+        if ((rc = trial_logl(ctx, a, stream))) return rc;
+        open_trial = true;
+        if (poll) {
+            HIP_TRY(ctx, hipStreamSynchronize(stream));
+            if (*ctx->h_ns_live == 0) { open_trial = false; break; }      // (no row proposed: there is nothing left to decide)
+        }
+    }
+    if (open_trial) {
+        a.it = o.max_steps + 1; a.decide = 1; a.propose = 0;
+        if ((rc = launch_ns(ctx, kNsStep, a, stream))) return rc;
+    }
+    if (r.theta) {                                      // the transformed rows of the points, as the cube launch forms them
+        const double *lo = ctx->d_prior, *hi = ctx->d_prior + ndim, *cube = r.U;
+        long total = (long)(nb * ndim);
+        int nd = ctx->ndim, slot = ctx->startind, as_int = ctx->prior_int;
+        double* theta = r.theta;
+        void* kargs[] = {(void*)&lo, (void*)&hi, (void*)&cube, (void*)&total, (void*)&nd, (void*)&slot, (void*)&as_int, (void*)&theta};
+        HIP_TRY(ctx, hipLaunchKernel(scale_cube_kernel_ptr(), dim3((unsigned)((total + 255) / 256)), dim3(256), kargs, 0, stream));
+    }
+    return MCALF_OK;
+}
+
+struct NsShard { NsRows r; const mcalf_slice_opts* o; int64_t ndim; };
+
+int ns_host(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o) {
+    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
+        NsShard c = {r, &o, ctx->ndim};
+        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
+            const NsShard* s = static_cast<const NsShard*>(arg);
+            const size_t o0 = (size_t)lo * s->ndim;
+            const NsRows part = {s->r.U0 + o0, s->r.Lmin + lo, s->r.D, s->r.sid + lo, s->r.U + o0, s->r.theta ? s->r.theta + o0 : nullptr,
+                                 s->r.logL + lo, s->r.status + lo, s->r.nevals + lo, s->r.moves + lo};
+            return ns_host(static_cast<mcalf_ctx*>(sub), part, hi - lo, *s->o);
+        }, &c);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(r.U0), is_pinned_host(r.U));
+    const size_t nb = (size_t)batch, n = nb * ctx->ndim, nd = (size_t)o.ndirs * ctx->ndim;
+    DevBuf<double>* b = ctx->nb;
+    int rc;
+    if ((rc = grow(ctx, b[mcalf_ctx::kNbU0], n)) || (rc = grow(ctx, b[mcalf_ctx::kNbU], n)) || (rc = grow(ctx, b[mcalf_ctx::kNbLmin], nb)) ||
+        (rc = grow(ctx, b[mcalf_ctx::kNbD], nd)) || (rc = grow(ctx, b[mcalf_ctx::kNbL], nb)) || (r.theta && (rc = grow(ctx, b[mcalf_ctx::kNbTheta], n))) ||
+        (rc = grow(ctx, ctx->ns_sid, nb)) || (rc = grow(ctx, ctx->ns_hst, 3 * nb)))
+        return rc;
+    const NsRows d = {b[mcalf_ctx::kNbU0], b[mcalf_ctx::kNbLmin], b[mcalf_ctx::kNbD], ctx->ns_sid, b[mcalf_ctx::kNbU],
+                      r.theta ? b[mcalf_ctx::kNbTheta].p : nullptr, b[mcalf_ctx::kNbL], ctx->ns_hst, ctx->ns_hst + nb, ctx->ns_hst + 2 * nb};
+    const hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kNbU0], r.U0, n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kNbLmin], r.Lmin, nb * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kNbD], r.D, nd * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ns_sid, r.sid, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if ((rc = run_ns(ctx, d, batch, o, st, true))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(r.U, d.U, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r.theta) HIP_TRY(ctx, hipMemcpyAsync(r.theta, d.theta, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r.logL, d.logL, nb * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r.status, d.status, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r.nevals, d.nevals, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r.moves, d.moves, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return MCALF_OK;
+}
+
+}  // namespace
+
+extern "C" int mcalf_slice_replace_batch(mcalf_ctx* ctx, const double* U0, const double* Lmin, const double* D, const uint64_t* sid,
+                                         int64_t batch, const mcalf_slice_opts* opts, double* U, double* theta, double* logL,
+                                         int32_t* status, int32_t* nevals, int32_t* moves) {
+    const NsRows r = {U0, Lmin, D, sid, U, theta, logL, status, nevals, moves};
+    const int rc = ns_check(ctx, "mcalf_slice_replace_batch", r, batch, opts, true);
+    if (rc || batch == 0) return rc;
+    return ns_host(ctx, r, batch, *opts);
+}
+
+extern "C" int mcalf_slice_replace_batch_device(mcalf_ctx* ctx, const double* dU0, const double* dLmin, const double* dD, const uint64_t* dsid,
+                                                int64_t batch, const mcalf_slice_opts* opts, double* dU, double* dtheta, double* dlogL,
+                                                int32_t* dstatus, int32_t* dnevals, int32_t* dmoves, void* stream) {
+    const NsRows r = {dU0, dLmin, dD, dsid, dU, dtheta, dlogL, dstatus, dnevals, dmoves};
+    const int rc = ns_check(ctx, "mcalf_slice_replace_batch_device", r, batch, opts, false);
+    if (rc) return rc;
+    MCALF_SINGLE_ONLY(ctx, "mcalf_slice_replace_batch_device");
+    if (batch == 0) return MCALF_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    begin_call(ctx, MCALF_PATH_DEVICE, false, false);
+    return run_ns(ctx, r, batch, *opts, (hipStream_t)stream, false);
+}

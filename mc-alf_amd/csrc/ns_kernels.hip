@@ -1,0 +1,174 @@
+// Device side of the nested-sampling replacement primitive (mcalf_slice_replace_batch), for gfx950: a batch of chains in the
+// unit cube, each moved by slice sampling along direction rows under a hard likelihood constraint L > Lmin.  The likelihood is
+// the cube logL launch's (kernels.hip, issued by host_ns.cpp between two kernels of this file); what lives here is the per-row
+// state machine that keeps the loop on the device: decide on the last trial, shrink the bracket or accept, propose the next.
+//
+//   ONE wave64 per row, lane k owns coordinates k, k + 64, ... (any ndim).  The chord of a line through the cube is a max /
+//   min over the coordinates: every lane folds its own, the 64 lane values go through one xor-butterfly (max and min are exact,
+//   so their order does not matter), and the row's scalars are made wave-uniform with readfirstlane.
+// The random words of a row are Philox4x64-10 of (step, stream id, seed): they depend on nothing else, so a row's bits depend
+// on its own start, constraint, stream id and the options alone -- not on its batch, its position or the device count.
+// Every product and sum of the proposal is a separately rounded multiply or add: contraction to FMA is switched off for this whole
+// file (hipcc contracts by default, and HIP's __dmul_rn / __dadd_rn are plain operators that it contracts all the same), so
+// that numpy restates a trajectory exactly (tests/ns_reference.py).  A finished row (status != 0) is carried: its point, its
+// logL and its counters stay as they are and its trial row is its own point.
+#include <hip/hip_runtime.h>
+
+#include "ns_args.h"
+
+#pragma clang fp contract(off)
+
+using namespace mcalf;
+
+namespace {
+
+__device__ __forceinline__ double uniform(double v) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const double o = __shfl_xor(v, m, 64);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const double o = __shfl_xor(v, m, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// Philox4x64-10 with counter (c0, 0, c2, 0) and key (k0, 0): words 0 and 1 of the block (2 and 3 are reserved).
+__device__ __forceinline__ void philox_words(uint64_t c0, uint64_t c2, uint64_t k0, uint64_t& w0, uint64_t& w1) {
+    uint64_t c1 = 0, c3 = 0, k1 = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t hi0 = __umul64hi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
+        const uint64_t hi1 = __umul64hi(kPhiloxM1, c2), lo1 = kPhiloxM1 * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += kPhiloxW0; k1 += kPhiloxW1;
+    }
+    w0 = c0; w1 = c1;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kNsWave) void mcalf_slice_start_kernel(const NsArgs a) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const size_t o = (size_t)row * a.ndim;
+    for (int k = lane; k < a.ndim; k += kNsWave) {
+        const double v = a.U0[o + k];
+        a.U[o + k] = v;
+        a.Y[o + k] = v;
+    }
+    if (lane == 0) {
+        a.status[row] = kNsLive;
+        a.nevals[row] = 0;
+        a.moves[row] = 0;
+        a.dir[row] = -1;
+    }
+}
+
+// A start is bad when an entry lies outside [0, 1] or is NaN, or when L(U0) > Lmin is false (NaN makes it false); it is returned
+// as given with the logL the launch gave it.  With nmoves == 0 a good start is finished at once.
+__global__ __launch_bounds__(kNsWave) void mcalf_slice_started_kernel(const NsArgs a) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const size_t o = (size_t)row * a.ndim;
+    int bad = 0;
+    for (int k = lane; k < a.ndim; k += kNsWave) {
+        const double v = a.U0[o + k];
+        bad |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+    }
+    const double l = a.LY[row];
+    const bool outside = __any(bad);
+    if (lane != 0) return;
+    a.L[row] = l;
+    if (outside || !(l > a.Lmin[row])) a.status[row] = kNsBadStart;
+    else if (a.nmoves == 0) a.status[row] = kNsDone;
+}
+
+__global__ __launch_bounds__(kNsWave) void mcalf_slice_step_kernel(const NsArgs a) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    if (__builtin_amdgcn_readfirstlane(a.status[row]) != kNsLive) return;
+    const size_t o = (size_t)row * a.ndim, n = (size_t)a.nrows;
+    double *x = a.U + o, *y = a.Y + o;
+    double tl = a.brk[row], tr = a.brk[n + row];
+    int dir = __builtin_amdgcn_readfirstlane(a.dir[row]);
+    if (a.decide) {
+        const double ly = a.LY[row];
+        if (ly > a.Lmin[row]) {                                // accepted: the trial row stays the row's own point
+            for (int k = lane; k < a.ndim; k += kNsWave) x[k] = y[k];
+            const int mv = a.moves[row] + 1;
+            dir = -1;
+            if (lane == 0) {
+                a.L[row] = ly;
+                a.moves[row] = mv;
+                a.dir[row] = -1;
+                if (mv == a.nmoves) a.status[row] = kNsDone;
+            }
+            if (mv == a.nmoves) return;
+        } else {                                               // rejected: the bracket shrinks towards t = 0, the current point
+            const double t = a.brk[2 * n + row];
+            if (t < 0.0) tl = t;
+            else tr = t;
+        }
+    }
+    if (!a.propose) return;
+    uint64_t w0, w1;
+    philox_words((uint64_t)a.it, a.sid[row], a.seed, w0, w1);
+    if (dir < 0) {                                             // a new direction: the chord of its line through the cube
+        dir = (int)(w0 % (uint64_t)a.ndirs);
+        const double* d = a.D + (size_t)dir * a.ndim;
+        double lo = -__builtin_inf(), hi = __builtin_inf();
+        int any = 0;
+        for (int k = lane; k < a.ndim; k += kNsWave) {
+            const double dk = d[k];
+            if (dk != 0.0) {
+                const double xa = (0.0 - x[k]) / dk, xb = (1.0 - x[k]) / dk;
+                const double mn = xa < xb ? xa : xb, mx = xa < xb ? xb : xa;
+                lo = mn > lo ? mn : lo;
+                hi = mx < hi ? mx : hi;
+                any = 1;
+            }
+        }
+        if (__any(any)) {
+            tl = uniform(wave_max(lo));
+            tr = uniform(wave_min(hi));
+        } else {
+            tl = tr = 0.0;
+        }
+    }
+    const double* d = a.D + (size_t)dir * a.ndim;
+    const double xi = (double)(w1 >> 11) * 0x1.0p-53;
+    const double t = tl + (tr - tl) * xi;
+    for (int k = lane; k < a.ndim; k += kNsWave) {
+        const double v = x[k] + t * d[k];
+        y[k] = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+    }
+    if (lane != 0) return;
+    a.brk[row] = tl;
+    a.brk[n + row] = tr;
+    a.brk[2 * n + row] = t;
+    a.dir[row] = dir;
+    a.nevals[row] += 1;
+    atomicAdd(a.live, 1u);
+}
+
+namespace mcalf {
+const void* ns_kernel_ptr(NsKernel k) {
+    static const void* const table[] = {(const void*)&mcalf_slice_start_kernel, (const void*)&mcalf_slice_started_kernel,
+                                        (const void*)&mcalf_slice_step_kernel};   // in the order of enum NsKernel
+    static_assert(sizeof(table) / sizeof(table[0]) == kNsKernelCount, "one entry per NsKernel");
+    return table[k];
+}
+}  // namespace mcalf

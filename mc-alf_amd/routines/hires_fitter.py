@@ -525,6 +525,51 @@ class als_fitter:
         P, logL, status, niter = self.maximize_batch(np.asarray(p0, dtype=float).reshape(1, -1), **kw)
         return P[0], float(logL[0]), int(status[0]), int(niter[0])
 
+    def slice_replace_batch(self, U0, Lmin, dirs, nmoves=None, max_steps=None, seed=0, stream_ids=None):
+        """(U, theta, logL, status, nevals, moves): nested sampling's replacement step on the device
+        (`mcalf_slice_replace_batch`; HIP kernels).  Every row of U0 (unit cube, [batch, ndim]) is a chain that makes
+        `nmoves` (None: 2 ndim) slice-sampling moves along rows of `dirs` ([ndirs, ndim], shared by all rows) under the
+        hard constraint logL > Lmin[row] (`Lmin`: a scalar or one value per row), in lock step for at most `max_steps`
+        (None: 50 nmoves) steps of one trial per row.
+
+        theta holds the transformed rows of U and logL[i] is `loglike_cube_batch(U)[i]` bit for bit.  status: 1 the row
+        made its moves, 0 `max_steps` reached (the row holds its last accepted point, which satisfies the constraint),
+        -1 the start lies outside the cube, has a NaN or does not satisfy the constraint (the row comes back as given).
+        nevals: trials the row evaluated; moves: accepted ones.  The random words of a row are Philox4x64-10 of (step,
+        stream_ids[row], seed) -- `stream_ids` (None: arange) must be distinct -- so a row's result does not depend on its
+        batch or its position."""
+        U0 = self._rows(U0, self.ndim)
+        n = U0.shape[0]
+        dirs = self._rows(dirs, self.ndim)
+        Lmin = np.ascontiguousarray(np.broadcast_to(np.asarray(Lmin, dtype=float), (n,)))
+        sid = np.arange(n, dtype=np.uint64) if stream_ids is None else np.ascontiguousarray(stream_ids, dtype=np.uint64).reshape(-1)
+        if sid.size != n:
+            raise ValueError(f"stream_ids must have one entry per row ({n}), got {sid.size}")
+        nmoves = 2 * self.ndim if nmoves is None else int(nmoves)
+        max_steps = 50 * nmoves if max_steps is None else int(max_steps)
+        self._ensure_prior()
+        opts = _lib.mcalf_slice_opts(nmoves, max_steps, dirs.shape[0], 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        U, theta = np.empty_like(U0), np.empty_like(U0)
+        logL = np.empty(n)
+        status, nevals, moves = (np.empty(n, dtype=np.int32) for _ in range(3))
+        _lib.check(self._lib.mcalf_slice_replace_batch(self._ctx, self._ptr(U0), self._ptr(Lmin), self._ptr(dirs), sid.ctypes.data, n,
+                                                       C.addressof(opts), self._ptr(U), self._ptr(theta), self._ptr(logL),
+                                                       status.ctypes.data, nevals.ctypes.data, moves.ctypes.data), self._ctx)
+        return U, theta, logL, status, nevals, moves
+
+    def nested_sample(self, nlive, batch=None, nmoves=None, dlogz=1e-3, max_rounds=100000, seed=0, max_steps=None):
+        """Nested sampling of this problem's posterior with the device's own two entries: `loglike_cube_batch` for the
+        initial live points and `slice_replace_batch` for every replacement round (`nested.nested_sample` keeps the books).
+        Returns a `nested.NestedResult`: logZ, logZ_err, H, the dead points with their log weights, and
+        `equal_weight_samples(rng)`, whose output goes into `write_equal_weights`."""
+        from .. import nested
+
+        def replace(U0, Lmin, dirs, nmoves, seed, stream_ids):
+            return self.slice_replace_batch(U0, Lmin, dirs, nmoves=nmoves, max_steps=max_steps, seed=seed, stream_ids=stream_ids)
+
+        return nested.nested_sample(lambda U: self.loglike_cube_batch(U), replace, self.ndim, nlive, batch=batch, nmoves=nmoves,
+                                    dlogz=dlogz, max_rounds=max_rounds, seed=seed)
+
     def loglike_hvp_batch(self, P, V, out=None):
         """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's
         `conv_mode` applied to one tangent per row ([batch, ndim] -> [batch, ndim]; HIP kernels, H is never formed).  It is
