@@ -86,7 +86,9 @@ extern "C" {
                                     mcalf_fisher_matvec_batch[_device], the Fisher product J^T W J v on the device, and
                                     mcalf_maximize_batch[_device], batched Levenberg-Marquardt maximisation of logL;
                                     mcalf_slice_replace_batch[_device], nested sampling's replacement step: batched slice
-                                    moves in the unit cube under a likelihood constraint) */
+                                    moves in the unit cube under a likelihood constraint;
+                                    mcalf_set_slice_compact, mcalf_slice_last_stats: the host entry of the replacement step
+                                    packs the rows that proposed a trial, and what a slice call launched) */
 
 enum {
     MCALF_OK = 0,
@@ -512,7 +514,8 @@ int mcalf_maximize_batch_device(mcalf_ctx* ctx, const double* dP0, int64_t batch
  * for bit, theta (optional, NULL: not wanted) holds the transformed rows of U as that entry forms them, nevals the trials the row
  * evaluated (its start not counted) and moves the accepted ones.  A row's results depend on its own (U0 row, Lmin, sid), on D and
  * on the options alone -- not on its batch, its position or the device count.  A step is one step kernel and one cube logL launch
- * (set-up kernel + fused kernel) over all rows, finished ones included. */
+ * (set-up kernel + fused kernel) over all rows, finished ones included (mcalf_set_slice_compact, below: over the rows that proposed
+ * a trial). */
 typedef struct {
     int32_t nmoves;          /* accepted moves per row, >= 0 (0: the checked start, status 1 or -1) */
     int32_t max_steps;       /* lock steps, >= 0 */
@@ -534,6 +537,31 @@ int mcalf_slice_replace_batch(mcalf_ctx* ctx, const double* U0, const double* Lm
 int mcalf_slice_replace_batch_device(mcalf_ctx* ctx, const double* dU0, const double* dLmin, const double* dD, const uint64_t* dsid,
                                      int64_t batch, const mcalf_slice_opts* opts, double* dU, double* dtheta, double* dlogL,
                                      int32_t* dstatus, int32_t* dnevals, int32_t* dmoves, void* stream);
+
+/* Packing the live rows.  0 (default): every lock step of mcalf_slice_replace_batch evaluates all rows.  1: the host entry packs
+ * the rows that proposed a trial -- a pack kernel lists them in ascending row order, a gather kernel copies their trial rows
+ * together -- and launches the cube logL over those only.  The launch of step `it` is sized by the count of step it - 1, which
+ * the host has read by then and which bounds the count of step it (rows only ever finish); the surplus slots evaluate the trial
+ * row of row 0 and are never read.  So the host waits for the 4-byte count of a step, not for the step's logL launch, and a call
+ * launches at most 2 batch + sum(nevals) rows instead of batch (1 + steps).  Results never depend on the setting, bit for bit:
+ * logL does not depend on a row's position or batch, and the random words are keyed by (step, stream id, seed).  Applies to every
+ * entry of a multi-device context.  The environment variable MCALF_NS_COMPACT (0 / 1) gives a context's initial value;
+ * mcalf_get_config prints "ns_compact=%d".  The *_device entry ignores it: it never synchronises, so it cannot size a launch by a
+ * device-side count.  ctx NULL or on outside {0, 1}: MCALF_ERR_INVALID. */
+int mcalf_set_slice_compact(mcalf_ctx* ctx, int32_t on);
+
+/* What the last mcalf_slice_replace_batch[_device] call of this context launched.  A multi-device context reports the sum over
+ * the entries the call was cut over for batch, rows_launched and trials, and the largest steps among them.  The device entry
+ * reports rows_launched = (max_steps + 1) batch (batch when nmoves == 0), trials = -1, steps = max_steps (0 when nmoves == 0) and
+ * compact = 0.  Before any slice call, and after one of batch 0, everything is 0.  ctx or out NULL: MCALF_ERR_INVALID. */
+typedef struct {
+    int64_t batch;          /* rows of the last slice call of this context */
+    int64_t rows_launched;  /* rows handed to cube logL launches by that call, the start launch included */
+    int64_t trials;         /* trials its rows proposed (= sum of nevals); -1 for the device entry (unknown to the host) */
+    int32_t steps;          /* lock steps whose logL launch was issued */
+    int32_t compact;        /* 1: the call packed its trial rows */
+} mcalf_slice_stats_t;      /* 32 bytes */
+int mcalf_slice_last_stats(const mcalf_ctx* ctx, mcalf_slice_stats_t* out);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -138,6 +138,16 @@ class mcalf_slice_opts(C.Structure):
     ]
 
 
+class mcalf_slice_stats_t(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int64),
+        ("rows_launched", C.c_int64),
+        ("trials", C.c_int64),
+        ("steps", C.c_int32),
+        ("compact", C.c_int32),
+    ]
+
+
 # status of a row of mcalf_slice_replace_batch
 MCALF_SLICE_MAXSTEPS, MCALF_SLICE_DONE, MCALF_SLICE_BAD_START = 0, 1, -1
 
@@ -188,6 +198,8 @@ SYMBOLS = {
     "mcalf_slice_replace_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]),
+    "mcalf_set_slice_compact": (C.c_int, [_CTX, C.c_int32]),
+    "mcalf_slice_last_stats": (C.c_int, [_CTX, C.POINTER(mcalf_slice_stats_t)]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

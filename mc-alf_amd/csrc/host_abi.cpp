@@ -78,6 +78,7 @@ extern "C" void mcalf_destroy(mcalf_ctx* ctx) {
     if (ctx->res_stream) (void)hipStreamDestroy(ctx->res_stream);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+    if (ctx->ev_ns) (void)hipEventDestroy(ctx->ev_ns);
     for (hipEvent_t e : ctx->ev_h2d)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_join)

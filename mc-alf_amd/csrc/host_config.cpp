@@ -49,6 +49,7 @@ EnvKnobs read_environment() {
         if (t > 0.0 && t <= 60.0) k.stream_timeout_s = t;
     }
     if (env_int("MCALF_CHUNKS", &v) && v >= 0 && v <= kMaxChunks) k.chunks = v;
+    if (env_int("MCALF_NS_COMPACT", &v) && (v == 0 || v == 1)) k.ns_compact = v;
     if (const char* e = std::getenv("MCALF_RCCL_LIB")) k.rccl_lib = e;
 #ifdef MCALF_TESTING
     if (env_int("MCALF_TEST_FAIL_PREFLIGHT", &v)) k.test_fail_preflight = v != 0;
@@ -80,6 +81,7 @@ void apply_environment(mcalf_ctx* ctx) {
     if (k.stream_trace >= 0) ctx->stream_trace = k.stream_trace;
     if (k.stream_timeout_s > 0.0) ctx->stream_timeout_s = k.stream_timeout_s;
     if (k.chunks >= 0) ctx->chunks_req = k.chunks;
+    if (k.ns_compact >= 0) ctx->ns_compact = k.ns_compact;
 #ifdef MCALF_TESTING
     if (k.test_fail_preflight >= 0) ctx->fail_preflight = k.test_fail_preflight != 0;
 #endif
@@ -102,7 +104,7 @@ extern "C" int mcalf_get_config(const mcalf_ctx* ctx, char* buf, int64_t n) {
     add("stream=%d stream_min=%d stream_wgs=%d stream_poll=%d stream_eager=%d stream_chunk=%d stream_device=%d stream_trace=%d stream_timeout_s=%g ",
         ctx->stream_on, ctx->stream_min, ctx->stream_wgs, ctx->stream_poll, ctx->stream_eager, ctx->stream_chunk, ctx->stream_device, ctx->stream_trace,
         ctx->stream_timeout_s);
-    add("xcd_mask=0x%x cu_mask_words=%d wide_lsf=%d", ctx->xcd_mask, (int)ctx->cu_mask.size(), ctx->wide);
+    add("xcd_mask=0x%x cu_mask_words=%d wide_lsf=%d ns_compact=%d", ctx->xcd_mask, (int)ctx->cu_mask.size(), ctx->wide, ctx->ns_compact);
     s += " [env:";
     auto named = [&](bool set, const char* name) { if (set) { s += ' '; s += name; } };
     named(k.lines_per_sync >= 0, "MCALF_LINES_PER_SYNC"); named(k.persist >= 0, "MCALF_PERSIST"); named(k.order >= 0, "MCALF_ORDER");
@@ -112,6 +114,7 @@ extern "C" int mcalf_get_config(const mcalf_ctx* ctx, char* buf, int64_t n) {
     named(k.stream_poll >= 0, "MCALF_STREAM_POLL"); named(k.stream_eager >= 0, "MCALF_STREAM_EAGER"); named(k.stream_chunk >= 0, "MCALF_STREAM_CHUNK");
     named(k.stream_device >= 0, "MCALF_STREAM_DEVICE"); named(k.stream_trace >= 0, "MCALF_STREAM_TRACE");
     named(k.stream_timeout_s > 0.0, "MCALF_STREAM_TIMEOUT"); named(k.chunks >= 0, "MCALF_CHUNKS"); named(!k.rccl_lib.empty(), "MCALF_RCCL_LIB");
+    named(k.ns_compact >= 0, "MCALF_NS_COMPACT");
     if (s.back() == ':') s += " none";
     s += "]";
     snprintf(buf, (size_t)n, "%s", s.c_str());

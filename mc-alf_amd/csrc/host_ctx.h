@@ -119,6 +119,7 @@ struct EnvKnobs {
     int stream_trace = -1;                  // MCALF_STREAM_TRACE     0 / 1
     double stream_timeout_s = -1.0;         // MCALF_STREAM_TIMEOUT   seconds, (0, 60]
     int chunks = -1;                        // MCALF_CHUNKS           0 .. 8
+    int ns_compact = -1;                    // MCALF_NS_COMPACT       0 / 1
     std::string rccl_lib;                   // MCALF_RCCL_LIB         (read when the first mcalf_comm_* call loads RCCL)
 #ifdef MCALF_TESTING
     int test_fail_preflight = -1;           // MCALF_TEST_FAIL_PREFLIGHT
@@ -305,13 +306,19 @@ struct mcalf_ctx {
     // evaluates, their logL [batch], the brackets [3][batch] and the direction index [batch] of one call; the host-pointer
     // entry's staging (starts, points, constraints, direction rows, logL, transformed rows; stream ids; status, nevals and
     // moves in ns_hst).  d_ns_live: the counter of rows that proposed a trial, which the host entry reads after every step
-    // through the page-locked word h_ns_live.
-    enum { kNbY, kNbLY, kNbBrk, kNbU0, kNbU, kNbLmin, kNbD, kNbL, kNbTheta, kNbCount };
+    // through the page-locked word h_ns_live.  ns_pack: the step stamps [batch] and, for a call that packs its trial rows
+    // (ns_compact, mcalf_set_slice_compact), their slots and the packed row list [batch] each; kNbYc: the packed trial rows;
+    // ev_ns: recorded behind the copy of the count, so that the host waits for the count and not for the step's logL launch.
+    // ns_stats: what the last slice call launched (mcalf_slice_last_stats; a multi-device parent holds the sum over its entries).
+    enum { kNbY, kNbLY, kNbBrk, kNbU0, kNbU, kNbLmin, kNbD, kNbL, kNbTheta, kNbYc, kNbCount };
     DevBuf<double> nb[kNbCount];
-    DevBuf<int32_t> ns_dir, ns_hst;
+    DevBuf<int32_t> ns_dir, ns_hst, ns_pack;
     DevBuf<uint64_t> ns_sid;
     DevBuf<unsigned int> d_ns_live;
     PinBuf<unsigned int> h_ns_live;
+    hipEvent_t ev_ns = nullptr;
+    int ns_compact = 0;                     // MCALF_NS_COMPACT / mcalf_set_slice_compact
+    mcalf_slice_stats_t ns_stats = {};
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).

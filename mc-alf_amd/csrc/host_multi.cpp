@@ -90,7 +90,7 @@ extern "C" int mcalf_create_multi(const mcalf_spec* spec, const int32_t* devices
     ctx->velstep = s0->velstep; ctx->asymm = s0->asymm; ctx->veto4 = s0->veto4; ctx->veto5 = s0->veto5;
     ctx->n_cap = s0->n_cap; ctx->tile = s0->tile; ctx->ntiles = s0->ntiles; ctx->ncl_cap = s0->ncl_cap; ctx->jax_half = s0->jax_half;
     ctx->selfhalo = s0->selfhalo; ctx->lps = s0->lps; ctx->wide = s0->wide; ctx->wide_n_cap = s0->wide_n_cap;
-    ctx->num_cu = s0->num_cu; ctx->xcd_mask = s0->xcd_mask;
+    ctx->num_cu = s0->num_cu; ctx->xcd_mask = s0->xcd_mask; ctx->ns_compact = s0->ns_compact;
     ctx->pool = new (std::nothrow) MultiPool();
     if (!ctx->pool) { multi_release(ctx); delete ctx; return set_err(nullptr, MCALF_ERR_NOMEM, "out of host memory"); }
     for (int k = 1; k < ndevices; ++k) {

@@ -2,7 +2,8 @@
 // chains in the unit cube moved by slice sampling under a hard likelihood constraint, in lock step.  A driver over the cube
 // logL launch (host_launch.cpp: launch() with from_cube) -- no Voigt code of its own.  One step is the step kernel (decide on
 // the last trial, propose the next) and one logL launch over the trial rows: the set-up kernel and the fused kernel, as
-// mcalf_loglike_cube_batch_device issues them.
+// mcalf_loglike_cube_batch_device issues them.  With mcalf_set_slice_compact on, the host entry's launch runs over the rows that
+// proposed a trial only (pack and gather kernels in between: compact_steps).  mcalf_slice_last_stats says what a call launched.
 #include <cmath>
 
 #include "ns_args.h"
@@ -41,52 +42,95 @@ int ns_check(mcalf_ctx* ctx, const char* name, const NsRows& r, int64_t batch, c
     return MCALF_OK;
 }
 
-int launch_ns(mcalf_ctx* ctx, NsKernel k, const NsArgs& a, hipStream_t stream) {
+int launch_ns(mcalf_ctx* ctx, NsKernel k, const NsArgs& a, hipStream_t stream, unsigned grid, unsigned block = kNsWave) {
     void* args[] = {(void*)&a};
-    HIP_TRY(ctx, hipLaunchKernel(ns_kernel_ptr(k), dim3((unsigned)a.nrows), dim3(kNsWave), args, 0, stream));
+    HIP_TRY(ctx, hipLaunchKernel(ns_kernel_ptr(k), dim3(grid), dim3(block), args, 0, stream));
     return MCALF_OK;
 }
 
-// logL of the trial rows, exactly what mcalf_loglike_cube_batch_device(Y) writes.
-int trial_logl(mcalf_ctx* ctx, const NsArgs& a, hipStream_t stream) {
-    LaunchReq q(kModeLogL, a.Y, a.nrows, stream);
-    q.d_out = const_cast<double*>(a.LY); q.from_cube = true;
+// logL of the `n` trial rows at Y into LY, exactly what mcalf_loglike_cube_batch_device(Y) writes.
+int trial_logl(mcalf_ctx* ctx, const double* Y, const double* LY, int64_t n, hipStream_t stream) {
+    LaunchReq q(kModeLogL, Y, n, stream);
+    q.d_out = const_cast<double*>(LY); q.from_cube = true;
     return launch(ctx, q);
+}
+
+// The lock steps of a call that packs its trial rows (mcalf_set_slice_compact; host entry only).  Live rows only ever finish, so
+// the count of rows that proposed in step it - 1 bounds the count of step it: the launch of step it is sized by it, and the host
+// reads the count of step it behind an event while the device is already in that step's logL launch -- the device never waits
+// for the host.  The slots past the count hold the trial row of row 0 and are never read.  *open_trial: the last trial has been
+// evaluated and not yet decided on.
+int compact_steps(mcalf_ctx* ctx, NsArgs& a, const mcalf_slice_opts& o, hipStream_t stream, bool* open_trial) {
+    mcalf_slice_stats_t& st = ctx->ns_stats;
+    int rc;
+    int64_t n = a.nrows;                                // count(0): every row may propose in step 1
+    for (int it = 1; it <= o.max_steps && o.nmoves > 0; ++it) {
+        a.it = it; a.decide = *open_trial ? 1 : 0; a.propose = 1;
+        if ((rc = launch_ns(ctx, kNsStep, a, stream, (unsigned)a.nrows)) || (rc = launch_ns(ctx, kNsPack, a, stream, 1, kNsPackBlock))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ns_live, a.live, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_ns, stream));
+        if ((rc = launch_ns(ctx, kNsGather, a, stream, (unsigned)n)) || (rc = trial_logl(ctx, a.Yc, a.LY, n, stream))) return rc;
+        *open_trial = true;
+        st.steps += 1; st.rows_launched += n;
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_ns));
+        const int64_t c = *ctx->h_ns_live;
+        st.trials += c;
+        if (c == 0) { *open_trial = false; break; }     // (no row proposed: there is nothing left to decide)
+        n = c;
+    }
+    return MCALF_OK;
 }
 
 // The call over `batch` device rows on `stream`.  poll: after every step the host reads the counter of rows that proposed a
 // trial (4 bytes, through a page-locked word) and leaves the loop at 0 -- finished rows are carried, so the rows' bits are those
-// of the unconditional max_steps steps the device entry runs.
+// of the unconditional max_steps steps the device entry runs.  A polling call of a context with ns_compact set packs its trial
+// rows (compact_steps); the rows' bits are the same again.
 int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o, hipStream_t stream, bool poll) {
     if (batch <= 0) return MCALF_OK;
     if (batch > 0x7fff0000LL) return set_err(ctx, MCALF_ERR_RANGE, "batch %lld too large", (long long)batch);
     const size_t nb = (size_t)batch, ndim = (size_t)ctx->ndim;
+    const bool compact = poll && ctx->ns_compact;
     int rc;
     if ((rc = grow(ctx, ctx->nb[mcalf_ctx::kNbY], nb * ndim)) || (rc = grow(ctx, ctx->nb[mcalf_ctx::kNbLY], nb)) ||
-        (rc = grow(ctx, ctx->nb[mcalf_ctx::kNbBrk], nb * kNsBrk)) || (rc = grow(ctx, ctx->ns_dir, nb)) || (rc = grow(ctx, ctx->d_ns_live, 1)))
+        (rc = grow(ctx, ctx->nb[mcalf_ctx::kNbBrk], nb * kNsBrk)) || (rc = grow(ctx, ctx->ns_dir, nb)) || (rc = grow(ctx, ctx->d_ns_live, 1)) ||
+        (rc = grow(ctx, ctx->ns_pack, nb * kNsPackInts)) || (compact && (rc = grow(ctx, ctx->nb[mcalf_ctx::kNbYc], nb * ndim))))
         return rc;
     if (poll && !ctx->h_ns_live.p) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->h_ns_live.p, sizeof(unsigned int), hipHostMallocDefault));
+    if (compact && !ctx->ev_ns) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_ns, hipEventDisableTiming));
+    mcalf_slice_stats_t& st = ctx->ns_stats;
+    st = mcalf_slice_stats_t();
+    st.batch = batch; st.rows_launched = batch; st.compact = compact ? 1 : 0;
     NsArgs a = {};
     a.U0 = r.U0; a.Lmin = r.Lmin; a.D = r.D; a.sid = r.sid; a.U = r.U; a.L = r.logL; a.status = r.status; a.nevals = r.nevals; a.moves = r.moves;
     a.Y = ctx->nb[mcalf_ctx::kNbY]; a.LY = ctx->nb[mcalf_ctx::kNbLY]; a.brk = ctx->nb[mcalf_ctx::kNbBrk]; a.dir = ctx->ns_dir; a.live = ctx->d_ns_live;
+    a.stamp = ctx->ns_pack;
     a.seed = o.seed; a.nrows = (int)batch; a.ndim = ctx->ndim; a.ndirs = o.ndirs; a.nmoves = o.nmoves;
-    if ((rc = launch_ns(ctx, kNsStart, a, stream)) || (rc = trial_logl(ctx, a, stream)) || (rc = launch_ns(ctx, kNsStarted, a, stream))) return rc;
+    const unsigned rows = (unsigned)batch;
+    if ((rc = launch_ns(ctx, kNsStart, a, stream, rows)) || (rc = trial_logl(ctx, a.Y, a.LY, batch, stream)) || (rc = launch_ns(ctx, kNsStarted, a, stream, rows))) return rc;
     bool open_trial = false;                            // the last trial has been evaluated and not yet decided on
-    for (int it = 1; it <= o.max_steps && o.nmoves > 0; ++it) {
-        if (poll) HIP_TRY(ctx, hipMemsetAsync(a.live, 0, sizeof(unsigned int), stream));
-        a.it = it; a.decide = open_trial ? 1 : 0; a.propose = 1;
-        if ((rc = launch_ns(ctx, kNsStep, a, stream))) return rc;
-        if (poll) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ns_live, a.live, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-        if ((rc = trial_logl(ctx, a, stream))) return rc;
-        open_trial = true;
-        if (poll) {
-            HIP_TRY(ctx, hipStreamSynchronize(stream));
-            if (*ctx->h_ns_live == 0) { open_trial = false; break; }      // (no row proposed: there is nothing left to decide)
+    if (compact) {                                      // (from here on LY holds the logL of the packed rows, by slot)
+        a.slot = ctx->ns_pack + nb; a.idx = ctx->ns_pack + 2 * nb; a.Yc = ctx->nb[mcalf_ctx::kNbYc];
+        if ((rc = compact_steps(ctx, a, o, stream, &open_trial))) return rc;
+    } else {
+        for (int it = 1; it <= o.max_steps && o.nmoves > 0; ++it) {
+            if (poll) HIP_TRY(ctx, hipMemsetAsync(a.live, 0, sizeof(unsigned int), stream));
+            a.it = it; a.decide = open_trial ? 1 : 0; a.propose = 1;
+            if ((rc = launch_ns(ctx, kNsStep, a, stream, rows))) return rc;
+            if (poll) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ns_live, a.live, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+            if ((rc = trial_logl(ctx, a.Y, a.LY, batch, stream))) return rc;
+            open_trial = true;
+            st.steps += 1; st.rows_launched += batch;
+            if (poll) {
+                HIP_TRY(ctx, hipStreamSynchronize(stream));
+                st.trials += *ctx->h_ns_live;
+                if (*ctx->h_ns_live == 0) { open_trial = false; break; }      // (no row proposed: there is nothing left to decide)
+            }
         }
+        if (!poll) st.trials = -1;                      // (the device entry never learns the counts)
     }
     if (open_trial) {
         a.it = o.max_steps + 1; a.decide = 1; a.propose = 0;
-        if ((rc = launch_ns(ctx, kNsStep, a, stream))) return rc;
+        if ((rc = launch_ns(ctx, kNsStep, a, stream, rows))) return rc;
     }
     if (r.theta) {                                      // the transformed rows of the points, as the cube launch forms them
         const double *lo = ctx->d_prior, *hi = ctx->d_prior + ndim, *cube = r.U;
@@ -104,13 +148,22 @@ struct NsShard { NsRows r; const mcalf_slice_opts* o; int64_t ndim; };
 int ns_host(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o) {
     if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
         NsShard c = {r, &o, ctx->ndim};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
+        const int rc = multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
             const NsShard* s = static_cast<const NsShard*>(arg);
             const size_t o0 = (size_t)lo * s->ndim;
             const NsRows part = {s->r.U0 + o0, s->r.Lmin + lo, s->r.D, s->r.sid + lo, s->r.U + o0, s->r.theta ? s->r.theta + o0 : nullptr,
                                  s->r.logL + lo, s->r.status + lo, s->r.nevals + lo, s->r.moves + lo};
             return ns_host(static_cast<mcalf_ctx*>(sub), part, hi - lo, *s->o);
         }, &c);
+        mcalf_slice_stats_t& st = ctx->ns_stats;          // the sum over the entries the call was cut over; the longest loop
+        st = mcalf_slice_stats_t();
+        st.compact = ctx->ns_compact;
+        for (int k = 0; k < ctx->multi_last_active; ++k) {
+            const mcalf_slice_stats_t& e = ctx->subs[k]->ns_stats;
+            st.batch += e.batch; st.rows_launched += e.rows_launched; st.trials += e.trials;
+            st.steps = std::max(st.steps, e.steps);
+        }
+        return rc;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(r.U0), is_pinned_host(r.U));
@@ -146,7 +199,9 @@ extern "C" int mcalf_slice_replace_batch(mcalf_ctx* ctx, const double* U0, const
                                          int32_t* status, int32_t* nevals, int32_t* moves) {
     const NsRows r = {U0, Lmin, D, sid, U, theta, logL, status, nevals, moves};
     const int rc = ns_check(ctx, "mcalf_slice_replace_batch", r, batch, opts, true);
-    if (rc || batch == 0) return rc;
+    if (rc) return rc;
+    ctx->ns_stats = mcalf_slice_stats_t();
+    if (batch == 0) return MCALF_OK;
     return ns_host(ctx, r, batch, *opts);
 }
 
@@ -157,8 +212,23 @@ extern "C" int mcalf_slice_replace_batch_device(mcalf_ctx* ctx, const double* dU
     const int rc = ns_check(ctx, "mcalf_slice_replace_batch_device", r, batch, opts, false);
     if (rc) return rc;
     MCALF_SINGLE_ONLY(ctx, "mcalf_slice_replace_batch_device");
+    ctx->ns_stats = mcalf_slice_stats_t();
     if (batch == 0) return MCALF_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     begin_call(ctx, MCALF_PATH_DEVICE, false, false);
     return run_ns(ctx, r, batch, *opts, (hipStream_t)stream, false);
+}
+
+extern "C" int mcalf_set_slice_compact(mcalf_ctx* ctx, int32_t on) {
+    if (!ctx) return set_err(nullptr, MCALF_ERR_INVALID, "mcalf_set_slice_compact: ctx is NULL");
+    if (on != 0 && on != 1) return set_err(ctx, MCALF_ERR_INVALID, "mcalf_set_slice_compact: on must be 0 or 1, got %d", on);
+    ctx->ns_compact = on;
+    for (mcalf_ctx* sub : ctx->subs) sub->ns_compact = on;
+    return MCALF_OK;
+}
+
+extern "C" int mcalf_slice_last_stats(const mcalf_ctx* ctx, mcalf_slice_stats_t* out) {
+    if (!ctx || !out) return set_err(nullptr, MCALF_ERR_INVALID, "mcalf_slice_last_stats: %s is NULL", !ctx ? "ctx" : "out");
+    *out = ctx->ns_stats;
+    return MCALF_OK;
 }

@@ -11,6 +11,8 @@ namespace mcalf {
 
 constexpr int kNsWave = 64;              // threads per workgroup: ONE wave per row (chain), lane k owns coordinates k, k + 64, ...
 constexpr int kNsBrk = 3;                // per-row bracket in `brk`: [0][rows] tl, [1][rows] tr, [2][rows] t of the trial
+constexpr int kNsPackBlock = 1024;       // threads of the pack kernel's ONE workgroup: rows it scans per pass
+constexpr int kNsPackInts = 3;           // per-row integers of the packing: [0][rows] stamp, [1][rows] slot, [2][rows] idx
 
 // Status of a row.  0 while it is live (and at the end: max_steps reached).
 enum { kNsLive = 0, kNsDone = 1, kNsBadStart = -1 };
@@ -32,18 +34,27 @@ struct NsArgs {
     const double* LY;         // logL of the trial rows [nrows], what it leaves
     double* brk;              // per-row bracket [kNsBrk][nrows]
     int32_t* dir;             // [nrows] the row of D the chain moves along; -1: the next proposal draws one
-    unsigned int* live;       // rows that proposed a trial in this step (integer counter)
+    unsigned int* live;       // rows that proposed a trial in this step (integer counter; the pack kernel stores its count here)
+    int32_t* stamp;           // [nrows] the step in which the row last proposed a trial; 0: not in this call
+    int32_t* slot;            // [nrows] where the row's trial sits among the packed rows of the step it proposed in.  NULL: the
+                              // trials are evaluated in place, LY is indexed by the row
+    int32_t* idx;             // [nrows] the packed rows of the step: idx[s] is the row of slot s, ascending
+    double* Yc;               // the packed trial rows [nrows, ndim], what the logL launch evaluates when the rows are packed
     uint64_t seed;
     int nrows, ndim, ndirs, nmoves;
     int it;                   // the step, 1 .. max_steps (+ 1: the last trial is decided, nothing is proposed)
     int decide, propose;
 };
 
-// The kernels of ns_kernels.hip; all take (const NsArgs a), grid = nrows, kNsWave threads.
+// The kernels of ns_kernels.hip; all take (const NsArgs a).  The row kernels: grid = nrows, kNsWave threads.
 enum NsKernel {
-    kNsStart,         // U = Y = U0, counters 0, no direction
+    kNsStart,         // U = Y = U0, counters 0, no direction, no stamp
     kNsStarted,       // after logL(Y): L = logL(U0); status -1 for a start outside the cube, with a NaN or not above Lmin
-    kNsStep,          // decide on the trial of step it - 1, propose the trial of step it
+    kNsStep,          // decide on the trial of step it - 1 (its logL at LY[slot ? slot[row] : row]), propose the trial of step
+                      // it and stamp the row with it
+    kNsPack,          // ONE workgroup of kNsPackBlock threads: the rows stamped `it`, ascending, into idx / slot; their count
+                      // into *live
+    kNsGather,        // grid = the launch size n >= *live, kNsWave threads: Yc[s] = Y[idx[s]], and Y row 0 for s >= *live
     kNsKernelCount
 };
 MCALF_INTERNAL const void* ns_kernel_ptr(NsKernel k);

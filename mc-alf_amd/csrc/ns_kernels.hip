@@ -12,6 +12,9 @@
 // file (hipcc contracts by default, and HIP's __dmul_rn / __dadd_rn are plain operators that it contracts all the same), so
 // that numpy restates a trajectory exactly (tests/ns_reference.py).  A finished row (status != 0) is carried: its point, its
 // logL and its counters stay as they are and its trial row is its own point.
+// Packing (mcalf_set_slice_compact): a row that proposes stamps itself with the step; the pack kernel lists the stamped rows in
+// row order (integers only), the gather kernel copies their trial rows together for a logL launch over those alone, and the
+// step kernel reads a trial's logL through the row's slot.  No row's bits depend on it.
 #include <hip/hip_runtime.h>
 
 #include "ns_args.h"
@@ -76,6 +79,7 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_start_kernel(const NsArgs
         a.nevals[row] = 0;
         a.moves[row] = 0;
         a.dir[row] = -1;
+        a.stamp[row] = 0;
     }
 }
 
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_step_kernel(const NsArgs 
     double tl = a.brk[row], tr = a.brk[n + row];
     int dir = __builtin_amdgcn_readfirstlane(a.dir[row]);
     if (a.decide) {
-        const double ly = a.LY[row];
+        const double ly = a.LY[a.slot ? a.slot[row] : row];
         if (ly > a.Lmin[row]) {                                // accepted: the trial row stays the row's own point
             for (int k = lane; k < a.ndim; k += kNsWave) x[k] = y[k];
             const int mv = a.moves[row] + 1;
@@ -161,13 +165,58 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_step_kernel(const NsArgs 
     a.brk[2 * n + row] = t;
     a.dir[row] = dir;
     a.nevals[row] += 1;
+    a.stamp[row] = a.it;                                        // (the step itself: nothing to clear between steps)
     atomicAdd(a.live, 1u);
+}
+
+// The rows that proposed a trial in step `it`, in ascending row order: idx[s] = row, slot[row] = s, *live = their count.  One
+// workgroup walks the rows kNsPackBlock at a time: a ballot and a popcount inside a wave, the wave sums through LDS, a running
+// base from pass to pass.  Integers only, no atomics: the order is the rows' own.
+__global__ __launch_bounds__(kNsPackBlock) void mcalf_slice_pack_kernel(const NsArgs a) {
+    constexpr int kWaves = kNsPackBlock / kNsWave;
+    __shared__ int wsum[kWaves];
+    const int tid = threadIdx.x, lane = tid & (kNsWave - 1), wave = tid / kNsWave;
+    int base = 0;
+    for (int r0 = 0; r0 < a.nrows; r0 += kNsPackBlock) {       // (nrows <= 0x7fff0000: r0 + tid stays an int)
+        const int row = r0 + tid;
+        const bool on = row < a.nrows && a.stamp[row] == a.it;
+        const unsigned long long m = __ballot(on);
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int before = base, total = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const int c = wsum[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (on) {
+            const int s = before + __popcll(m & ((1ull << lane) - 1ull));
+            a.idx[s] = row;
+            a.slot[row] = s;
+        }
+        base += total;
+        __syncthreads();                                       // (wsum is written again by the next pass)
+    }
+    if (tid == 0) *a.live = (unsigned int)base;
+}
+
+// One wave per slot of the launch: the trial row of the slot's chain, and the trial row of row 0 -- a row the unpacked launch
+// evaluates all the same -- for the slots past the count, whose logL nobody reads.
+__global__ __launch_bounds__(kNsWave) void mcalf_slice_gather_kernel(const NsArgs a) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int count = (int)__builtin_amdgcn_readfirstlane((int)*a.live);
+    const int row = s < count ? __builtin_amdgcn_readfirstlane(a.idx[s]) : 0;
+    const double* y = a.Y + (size_t)row * a.ndim;
+    double* yc = a.Yc + (size_t)s * a.ndim;
+    for (int k = lane; k < a.ndim; k += kNsWave) yc[k] = y[k];
 }
 
 namespace mcalf {
 const void* ns_kernel_ptr(NsKernel k) {
     static const void* const table[] = {(const void*)&mcalf_slice_start_kernel, (const void*)&mcalf_slice_started_kernel,
-                                        (const void*)&mcalf_slice_step_kernel};   // in the order of enum NsKernel
+                                        (const void*)&mcalf_slice_step_kernel, (const void*)&mcalf_slice_pack_kernel,
+                                        (const void*)&mcalf_slice_gather_kernel};   // in the order of enum NsKernel
     static_assert(sizeof(table) / sizeof(table[0]) == kNsKernelCount, "one entry per NsKernel");
     return table[k];
 }

@@ -25,7 +25,11 @@ class NestedResult:
     logw                  their log posterior weights, normalised: sum(exp(logw)) == 1
     rounds, nevals        replacement rounds; likelihood evaluations (the initial points and every trial of every chain)
     unfinished            rows a replacement call returned with status 0 (kept: they satisfy their constraint)
+    rows_launched         rows handed to likelihood launches, carried finished rows included (None: the `replace` callable does
+                          not say; `als_fitter.nested_sample` fills it in from `slice_stats()`)
     nlive"""
+
+    rows_launched = None
 
     def __init__(self, **kw):
         self.__dict__.update(kw)

@@ -557,18 +557,40 @@ class als_fitter:
                                                        status.ctypes.data, nevals.ctypes.data, moves.ctypes.data), self._ctx)
         return U, theta, logL, status, nevals, moves
 
+    def set_slice_compact(self, on):
+        """Packing of the live rows in `slice_replace_batch` (`mcalf_set_slice_compact`; off by default, MCALF_NS_COMPACT gives
+        the initial value).  On: every lock step launches the likelihood over the rows that proposed a trial only, instead of
+        over all rows of the call.  Results never depend on it, bit for bit; `slice_stats()` shows what it saves."""
+        _lib.check(self._lib.mcalf_set_slice_compact(self._ctx, int(bool(on))), self._ctx)
+
+    def slice_stats(self):
+        """What the last `slice_replace_batch` call launched (`mcalf_slice_last_stats`), as a dict: `batch` its rows,
+        `rows_launched` the rows handed to likelihood launches (the start launch included), `trials` the trials its rows
+        proposed (the sum of nevals), `steps` the lock steps issued, `compact` whether the call packed its trial rows.
+        All 0 before the first call."""
+        st = _lib.mcalf_slice_stats_t()
+        _lib.check(self._lib.mcalf_slice_last_stats(self._ctx, C.byref(st)), self._ctx)
+        return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
     def nested_sample(self, nlive, batch=None, nmoves=None, dlogz=1e-3, max_rounds=100000, seed=0, max_steps=None):
         """Nested sampling of this problem's posterior with the device's own two entries: `loglike_cube_batch` for the
         initial live points and `slice_replace_batch` for every replacement round (`nested.nested_sample` keeps the books).
         Returns a `nested.NestedResult`: logZ, logZ_err, H, the dead points with their log weights, and
-        `equal_weight_samples(rng)`, whose output goes into `write_equal_weights`."""
+        `equal_weight_samples(rng)`, whose output goes into `write_equal_weights`.  Its `rows_launched` counts the rows
+        handed to likelihood launches: nlive for the initial points and `slice_stats()["rows_launched"]` of every round
+        (`set_slice_compact(True)` lowers it; nothing else of the result depends on that setting)."""
         from .. import nested
+        launched = [int(nlive)]
 
         def replace(U0, Lmin, dirs, nmoves, seed, stream_ids):
-            return self.slice_replace_batch(U0, Lmin, dirs, nmoves=nmoves, max_steps=max_steps, seed=seed, stream_ids=stream_ids)
+            out = self.slice_replace_batch(U0, Lmin, dirs, nmoves=nmoves, max_steps=max_steps, seed=seed, stream_ids=stream_ids)
+            launched[0] += self.slice_stats()["rows_launched"]
+            return out
 
-        return nested.nested_sample(lambda U: self.loglike_cube_batch(U), replace, self.ndim, nlive, batch=batch, nmoves=nmoves,
-                                    dlogz=dlogz, max_rounds=max_rounds, seed=seed)
+        res = nested.nested_sample(lambda U: self.loglike_cube_batch(U), replace, self.ndim, nlive, batch=batch, nmoves=nmoves,
+                                   dlogz=dlogz, max_rounds=max_rounds, seed=seed)
+        res.rows_launched = launched[0]
+        return res
 
     def loglike_hvp_batch(self, P, V, out=None):
         """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's

@@ -3,14 +3,17 @@ chains.  nlive = 4 K uniform points of the cube; every round the K lowest die an
 under the K-th dead point's logL (directions: Cholesky factor of the survivors' covariance), as `nested.nested_sample` does.
 The first --burn rounds (device route only, not timed) compress the live points, so that the timed rounds see a constraint that
 rejects trials; round 0 warms both routes up.
-Two routes through the same state machine, on the same inputs, alternating within one run (which goes first changes every round):
+Three routes through the same state machine, on the same inputs, alternating within one run (the order rotates every round):
   device  `slice_replace_batch` (host entry: H2D, the lock steps with the 4-byte count of live rows read after every step, D2H;
           wall clock) and mcalf_slice_replace_batch_device between HIP events on one stream (the steps the host entry ran);
+  packed  the same host entry with `set_slice_compact(True)`: every step's logL launch runs over the rows that proposed a trial
+          (sized by the count of the step before), not over all K (wall clock);
   numpy   what the library offered before: the numpy restatement of the state machine (tests/ns_reference.py) around
           `loglike_cube_batch`, one host round trip per step (wall clock).
-Recorded per round: lock steps, ms per step and per round of each route, and the lock-step waste -- the share of evaluated rows
-that were already finished, 1 - sum(nevals) / (steps K).  The two routes must agree bit for bit (exit status 1 otherwise).  One
-JSON line, also written to --out.
+Recorded per round: lock steps, ms per step and per round of each route, the rows each host-entry route handed to logL launches
+and the trials (`slice_stats`), and the lock-step waste -- the share of evaluated rows that were already finished,
+1 - sum(nevals) / (steps K).  Per run: the median over the timed rounds, and their minimum and maximum.  The routes must agree
+bit for bit (exit status 1 otherwise).  One JSON line, also written to --out.
 python tools/ns_timing.py [--configs C,B] [--chains 1024,4096] [--rounds 5] [--burn 20] [--nmoves 8] [--max-steps 400] [--out profiles/ns_timing.json]"""
 import argparse
 import ctypes as C
@@ -77,15 +80,24 @@ def _run(fit, K, rounds, nmoves, max_steps, seed, burn):
             Un, _, Ln, _, _, _ = fit.slice_replace_batch(U0, lmin, D, nmoves=nmoves, max_steps=max_steps, seed=seed, stream_ids=sid)
             U[dying], L[dying] = Un, Ln
             continue
-        t = {}
-        for route in (("device", "numpy") if r % 2 else ("numpy", "device")):
+        t, stats = {}, {}
+        routes = ("device", "packed", "numpy")
+        for route in routes[r % 3:] + routes[:r % 3]:
+            fit.set_slice_compact(route == "packed")
             t0 = time.perf_counter()
             if route == "device":
                 got = fit.slice_replace_batch(U0, lmin, D, nmoves=nmoves, max_steps=max_steps, seed=seed, stream_ids=sid)
+            elif route == "packed":
+                packed = fit.slice_replace_batch(U0, lmin, D, nmoves=nmoves, max_steps=max_steps, seed=seed, stream_ids=sid)
             else:
                 ref = nr.slice_replace(logl, U0, lmin, D, sid, nmoves, max_steps, seed)
             t[route] = (time.perf_counter() - t0) * 1e3
+            stats[route] = fit.slice_stats()
+        fit.set_slice_compact(False)
         Un, _, Ln, status, nevals, moves = got
+        same &= all(a.tobytes() == b.tobytes() for a, b in zip(got, packed))
+        same &= stats["device"]["compact"] == 0 and stats["packed"]["compact"] == 1
+        same &= stats["device"]["trials"] == stats["packed"]["trials"] == int(nevals.sum())
         steps = int(nevals.max())
         t_dev, dev = _device_entry_ms(fit, U0, lmin, D, sid, nmoves, steps, seed)
         same &= all(a.tobytes() == b.tobytes() for a, b in zip((Ln, status, nevals, moves), ref[1:])) and np.array_equal(Un, ref[0])
@@ -96,11 +108,17 @@ def _run(fit, K, rounds, nmoves, max_steps, seed, burn):
         rows.append({"round": r, "lock_steps": steps, "evaluations_per_row_mean": round(float(nevals.mean()), 2),
                      "lock_step_waste": round(1.0 - float(nevals.sum()) / (steps * K), 4), "unfinished_rows": int((status == 0).sum()),
                      "host_entry_ms": round(t["device"], 2), "host_entry_ms_per_step": round(t["device"] / steps, 4),
+                     "host_entry_rows_launched": stats["device"]["rows_launched"],
+                     "packed_entry_ms": round(t["packed"], 2), "packed_entry_ms_per_step": round(t["packed"] / steps, 4),
+                     "packed_entry_rows_launched": stats["packed"]["rows_launched"], "trials": stats["packed"]["trials"],
+                     "host_over_packed_entry": round(t["device"] / t["packed"], 3),
                      "device_entry_ms": round(t_dev, 2), "device_entry_ms_per_step": round(t_dev / steps, 4),
                      "numpy_route_ms": round(t["numpy"], 2), "numpy_route_ms_per_step": round(t["numpy"] / steps, 4),
                      "numpy_over_host_entry": round(t["numpy"] / t["device"], 2)})
-    med = {k: round(float(np.median([q[k] for q in rows])), 4) for k in rows[0] if k != "round"} if rows else {}
-    return rows, med, same
+    keys = [k for k in rows[0] if k != "round"] if rows else []
+    med = {k: round(float(np.median([q[k] for q in rows])), 4) for k in keys}
+    spread = {k: [min(q[k] for q in rows), max(q[k] for q in rows)] for k in keys if k.endswith(("_ms", "_ms_per_step", "_rows_launched"))}
+    return rows, med, spread, same
 
 
 def main():
@@ -118,10 +136,10 @@ def main():
         kw, _, seed = workloads.config(name, _synth)
         with mcalf_amd.als_fitter(None, **kw) as fit:
             for K in (int(k) for k in args.chains.split(",")):
-                rows, med, ok = _run(fit, K, args.rounds, args.nmoves, args.max_steps, seed, args.burn)
+                rows, med, spread, ok = _run(fit, K, args.rounds, args.nmoves, args.max_steps, seed, args.burn)
                 same &= ok
                 out["runs"].append({"config": name, "npix": int(fit.obj_wl.size), "ndim": int(fit.ndim), "chains": K, "nlive": 4 * K,
-                                    "routes_agree_bit_for_bit": ok, "median_over_rounds": med, "rounds": rows})
+                                    "routes_agree_bit_for_bit": ok, "median_over_rounds": med, "min_max_over_rounds": spread, "rounds": rows})
     line = json.dumps(out)
     print(line)
     if args.out:
