@@ -88,7 +88,9 @@ extern "C" {
                                     mcalf_slice_replace_batch[_device], nested sampling's replacement step: batched slice
                                     moves in the unit cube under a likelihood constraint;
                                     mcalf_set_slice_compact, mcalf_slice_last_stats: the host entry of the replacement step
-                                    packs the rows that proposed a trial, and what a slice call launched) */
+                                    packs the rows that proposed a trial, and what a slice call launched;
+                                    mcalf_ensemble_batch[_device], the ensemble MCMC sampler: stretch and DE moves of a walker
+                                    set in the unit cube, the chain kept on the device) */
 
 enum {
     MCALF_OK = 0,
@@ -562,6 +564,59 @@ typedef struct {
     int32_t compact;        /* 1: the call packed its trial rows */
 } mcalf_slice_stats_t;      /* 32 bytes */
 int mcalf_slice_last_stats(const mcalf_ctx* ctx, mcalf_slice_stats_t* out);
+
+/* The ensemble sampler: n = nwalkers walkers in the unit cube of mcalf_set_prior's box (MCALF_ERR_INVALID if none is set), cut
+ * into the halves [0, m) and [m, n), m = n / 2 (n even, >= 4).  logL is exactly mcalf_loglike_cube_batch's value.  One iteration
+ * is two half-steps h = 0, 1; in half-step h the walkers of half h move, with partners from the other half as it stands then.
+ *   start    logL(U0) by one cube launch over all n rows.  A walker whose start has an entry outside [0, 1] or a NaN has
+ *            status -1 and never moves: its row is returned as given (others may still draw it as a partner; such proposals are
+ *            decided by the rules below).  Every other walker has status 0.
+ *   words    for moving walker w (its index among the n) and global half-step s = 2 (first_iter + i) + h, i the iteration within
+ *            the call: (w0, w1, w2, w3) = the block numpy's Philox(counter=[s, 0, w, 0], key=[seed, 1]) returns first, with the
+ *            constants of the slice step above.  That generator advances its counter before it draws (the slice step's block of
+ *            step 1 is the first of counter 0 in the same way), so it is the Philox4x64-10 function at counter (s + 1, 0, w, 0).
+ *            xi = (w1 >> 11) 2^-53;  zeta = ((w2 >> 11) + 1) 2^-53, in (0, 1].
+ *   stretch  (MCALF_ENS_STRETCH, scale = a > 1)  j = the other half's first index + w0 mod m;  t = (a - 1) xi + 1,  z = t t / a;
+ *            y_k = x_j,k + z (x_k - x_j,k);  q = (ndim - 1) ln z + (logL(y) - logL(x)).
+ *   DE       (MCALF_ENS_DE, scale = g > 0)  j1 = w0 mod m, j2 = (j1 + 1 + w3 mod (m - 1)) mod m, both in the other half;
+ *            gamma = g (1 + 1e-5 (2 xi - 1));  y_k = x_k + gamma (x_j1,k - x_j2,k);  q = logL(y) - logL(x)  (a symmetric move).
+ *   decide   y is inside iff every 0 <= y_k <= 1 (a NaN fails).  A walker whose y is not inside puts its own point in its trial
+ *            row and is rejected whatever the launch returns.  Otherwise it is accepted iff ln zeta < q (any NaN: false):
+ *            x <- y, logL <- logL(y), naccept + 1.
+ *   ln       for normal positive x = f 2^e, f in [1, 2) from the bits:  if f > 0x1.6a09e667f3bcdp+0: f <- 0.5 f, e <- e + 1;
+ *            r = (f - 1) / (f + 1);  s = r r;  p = 1/19, then p <- p s + 1 / (2 i + 1) for i = 8 .. 1;  t = r + r;
+ *            lnf = t + (t s) p;  ln x = e 0x1.62e42feep-1 + (lnf + e 0x1.a39ef35793c76p-33).  Within 1e-13 of the true
+ *            logarithm, relatively (measured: DESIGN 3.13); zeta >= 2^-53 and z in [1 / a, a] are normal.
+ *   chain    after every iteration i with (i + 1) mod thin == 0 the device copies the state into slot (i + 1) / thin - 1 of
+ *            CU [nkeep][n][ndim] and CL [nkeep][n], nkeep = nsteps / thin: a run of any length reaches the host once.
+ * Every product, quotient, sum and difference above is ONE correctly rounded IEEE operation (nothing is contracted to an FMA)
+ * and there are no floating-point atomics, so a run can be restated exactly on the host; a walker's results depend on (U0, opts)
+ * alone.  Taking the last U as U0 with first_iter advanced by nsteps is, bit for bit, the longer call.  A half-step is a propose
+ * kernel over the m moving walkers, one cube logL launch over their m trial rows and a decide kernel (which also fills the
+ * chain slot).  theta (optional) holds the transformed rows of U as the cube launch forms them. */
+enum { MCALF_ENS_STRETCH = 0, MCALF_ENS_DE = 1 };
+typedef struct {
+    int32_t nsteps;          /* iterations, >= 0 (0: the checked start and its logL) */
+    int32_t thin;            /* every thin-th iteration goes into the chain, >= 1 */
+    int32_t move;            /* MCALF_ENS_STRETCH or MCALF_ENS_DE */
+    int32_t reserved;
+    double scale;            /* a > 1 of the stretch move, g > 0 of the DE move; finite */
+    uint64_t seed;           /* the Philox key word 0 */
+    uint64_t first_iter;     /* the iteration number of the call's first iteration (continuation) */
+} mcalf_ens_opts;            /* 40 bytes */
+/* Host pointers, synchronous: U, theta (n x ndim; theta NULL: not wanted), logL, status, naccept (n each) and the chain CU, CL
+ * (each NULL: not wanted) are outputs; U0 and U must not overlap.  A multi-device context runs the whole call on its first device
+ * entry (the walkers have to meet on one device): bit for bit a single-device context's result.  All argument checks (ctx, opts
+ * or a required array NULL; nwalkers negative, odd, or below 4 when non-zero; nsteps < 0; thin < 1; move outside {0, 1}; scale not
+ * finite, <= 1 for the stretch move, <= 0 for the DE move; no prior set) come before any device work and name the argument.
+ * A chain above 4 GiB on the device is MCALF_ERR_RANGE (the message names the largest nkeep).  nwalkers == 0 does nothing. */
+int mcalf_ensemble_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, const mcalf_ens_opts* opts, double* U, double* theta,
+                         double* logL, int32_t* status, int32_t* naccept, double* CU, double* CL);
+/* Same, device pointers (opts is a host struct, read during the call), on the caller's stream (single-device contexts).  It never
+ * synchronises; the bits are the host entry's.  After one call of the same or a larger size it allocates nothing. */
+int mcalf_ensemble_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const mcalf_ens_opts* opts, double* dU,
+                                double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept, double* dCU, double* dCL,
+                                void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -9,6 +9,7 @@ from . import _lib  # noqa: F401
 from . import adapters  # noqa: F401
 from . import broker  # noqa: F401
 from . import dist  # noqa: F401
+from . import ensemble  # noqa: F401
 from . import nested  # noqa: F401
 from . import routines  # noqa: F401
 from . import workloads  # noqa: F401

@@ -148,6 +148,21 @@ class mcalf_slice_stats_t(C.Structure):
     ]
 
 
+class mcalf_ens_opts(C.Structure):
+    _fields_ = [
+        ("nsteps", C.c_int32),
+        ("thin", C.c_int32),
+        ("move", C.c_int32),
+        ("reserved", C.c_int32),
+        ("scale", C.c_double),
+        ("seed", C.c_uint64),
+        ("first_iter", C.c_uint64),
+    ]
+
+
+# the moves of mcalf_ensemble_batch
+MCALF_ENS_STRETCH, MCALF_ENS_DE = 0, 1
+
 # status of a row of mcalf_slice_replace_batch
 MCALF_SLICE_MAXSTEPS, MCALF_SLICE_DONE, MCALF_SLICE_BAD_START = 0, 1, -1
 
@@ -200,6 +215,10 @@ SYMBOLS = {
                                                   C.c_void_p]),
     "mcalf_set_slice_compact": (C.c_int, [_CTX, C.c_int32]),
     "mcalf_slice_last_stats": (C.c_int, [_CTX, C.POINTER(mcalf_slice_stats_t)]),
+    "mcalf_ensemble_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_ensemble_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -1,0 +1,158 @@
+// Device side of the ensemble sampler (mcalf_ensemble_batch), for gfx950: n walkers in the unit cube, cut into the halves
+// [0, m) and [m, n), moved by the affine-invariant stretch move or by the differential-evolution move with partners from the
+// half that stands still.  The likelihood is the cube logL launch's (kernels.hip, issued by host_ens.cpp between the propose
+// and the decide kernel of a half-step); what lives here is the proposal, the accept rule and the chain.
+//
+//   ONE wave64 per walker, lane k owns coordinates k, k + 64, ... (any ndim).  The inside-the-cube test folds every turn of the
+//   lane's loop and is made wave-uniform by a ballot.  The scalars of a walker (its random words, z or gamma, ln z, ln zeta)
+//   are computed by every lane alike.
+// The random words of moving walker w in global half-step s are the block numpy's Philox(counter=[s, 0, w, 0], key=[seed, 1])
+// returns first: that generator advances its counter before it draws, so the block is Philox4x64-10 at (s + 1, 0, w, 0) -- as
+// the slice step's word block of step 1 is the first one of Philox(counter=[0, 0, sid, 0]).  The words depend on nothing else,
+// so a walker's results depend on the starts and the options alone.
+// Every product, quotient, sum and difference of the proposal, of ens_ln and of the accept rule is a separately rounded IEEE
+// operation: contraction to FMA is switched off for this whole file (as in ns_kernels.hip), so that numpy restates a run exactly
+// (tests/ens_reference.py).  No atomics.
+#include <hip/hip_runtime.h>
+
+#include "ens_args.h"
+
+#pragma clang fp contract(off)
+
+using namespace mcalf;
+
+namespace {
+
+// Philox4x64-10 with counter (c0, 0, c2, 0) and key (k0, k1): the four words of the block.
+__device__ __forceinline__ void philox_block(uint64_t c0, uint64_t c2, uint64_t k0, uint64_t k1, uint64_t (&w)[4]) {
+    uint64_t c1 = 0, c3 = 0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t hi0 = __umul64hi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
+        const uint64_t hi1 = __umul64hi(kPhiloxM1, c2), lo1 = kPhiloxM1 * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += kPhiloxW0; k1 += kPhiloxW1;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+// ln x for normal positive x: the sequence of ens_args.h, operation for operation.
+__device__ __forceinline__ double ens_ln(double x) {
+    const long long b = __double_as_longlong(x);
+    int e = (int)((b >> 52) & 0x7ff) - 1023;
+    double f = __longlong_as_double((b & 0x000fffffffffffffLL) | 0x3ff0000000000000LL);
+    if (f > kEnsSqrt2) { f = f * 0.5; e += 1; }
+    const double r = (f - 1.0) / (f + 1.0);
+    const double s = r * r;
+    double p = 1.0 / (2 * kEnsLnTerms + 1);
+#pragma unroll
+    for (int i = kEnsLnTerms - 1; i >= 1; --i) p = p * s + 1.0 / (2 * i + 1);
+    const double t = r + r;
+    const double lnf = t + (t * s) * p;
+    const double ed = (double)e;
+    return ed * kEnsLn2Hi + (lnf + ed * kEnsLn2Lo);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kEnsWave) void mcalf_ens_start_kernel(const EnsArgs a) {
+    const int w = blockIdx.x, lane = threadIdx.x;
+    const size_t o = (size_t)w * a.ndim;
+    int bad = 0;
+    for (int k = lane; k < a.ndim; k += kEnsWave) {
+        const double v = a.U0[o + k];
+        a.U[o + k] = v;
+        bad |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+    }
+    const bool outside = __any(bad);
+    if (lane != 0) return;
+    a.status[w] = outside ? kEnsBadStart : kEnsOk;
+    a.naccept[w] = 0;
+}
+
+__global__ __launch_bounds__(kEnsWave) void mcalf_ens_propose_kernel(const EnsArgs a) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int w = a.half * a.m + b, other = (1 - a.half) * a.m;
+    const double* x = a.U + (size_t)w * a.ndim;
+    double* y = a.Y + (size_t)b * a.ndim;
+    const bool moves = __builtin_amdgcn_readfirstlane(a.status[w]) == kEnsOk;
+    uint64_t wd[4];
+    philox_block(a.step + 1, (uint64_t)w, a.seed, kEnsKey1, wd);      // (numpy's generator draws at counter + 1)
+    const uint64_t m = (uint64_t)a.m;
+    const double xi = (double)(wd[1] >> 11) * 0x1.0p-53;
+    const double zeta = (double)((wd[2] >> 11) + 1) * 0x1.0p-53;
+    double hastings = 0.0;
+    int out = 0;
+    if (!moves) {
+        out = 1;
+    } else if (a.move == kEnsStretch) {
+        const double* xj = a.U + (size_t)(other + (int)(wd[0] % m)) * a.ndim;
+        const double t = (a.scale - 1.0) * xi + 1.0;
+        const double z = (t * t) / a.scale;
+        hastings = (double)(a.ndim - 1) * ens_ln(z);
+        for (int k = lane; k < a.ndim; k += kEnsWave) {
+            const double pj = xj[k];
+            const double v = pj + z * (x[k] - pj);
+            y[k] = v;
+            out |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+        }
+    } else {
+        const uint64_t j1 = wd[0] % m, j2 = (j1 + 1 + wd[3] % (m - 1)) % m;
+        const double* x1 = a.U + (size_t)(other + (int)j1) * a.ndim;
+        const double* x2 = a.U + (size_t)(other + (int)j2) * a.ndim;
+        const double gamma = a.scale * (1.0 + 1e-5 * (2.0 * xi - 1.0));
+        for (int k = lane; k < a.ndim; k += kEnsWave) {
+            const double v = x[k] + gamma * (x1[k] - x2[k]);
+            y[k] = v;
+            out |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+        }
+    }
+    const bool outside = __any(out);
+    if (outside)                                               // the trial row is the walker's own point, as a finished slice row's
+        for (int k = lane; k < a.ndim; k += kEnsWave) y[k] = x[k];
+    if (lane != 0) return;
+    a.aux[b] = hastings;
+    a.aux[(size_t)a.m + b] = ens_ln(zeta);
+    a.inside[b] = outside ? 0 : 1;
+}
+
+__global__ __launch_bounds__(kEnsWave) void mcalf_ens_decide_kernel(const EnsArgs a) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int w = a.half * a.m + b;
+    double* x = a.U + (size_t)w * a.ndim;
+    if (__builtin_amdgcn_readfirstlane(a.inside[b])) {
+        const double* y = a.Y + (size_t)b * a.ndim;
+        const double ly = a.LY[b], lx = a.L[w];
+        const double d = ly - lx;
+        const double q = a.move == kEnsStretch ? a.aux[b] + d : d;
+        if (a.aux[(size_t)a.m + b] < q) {                      // (any NaN: false)
+            for (int k = lane; k < a.ndim; k += kEnsWave) x[k] = y[k];
+            if (lane == 0) {
+                a.L[w] = ly;
+                a.naccept[w] += 1;
+            }
+        }
+    }
+    if (!a.keep) return;
+    // The state after the iteration (half 1 has just decided): walker b stood still in this half-step, and what this wave wrote
+    // of walker m + b above is read back by the lane that wrote it.
+    for (int r = 0; r < 2; ++r) {
+        const int v = r * a.m + b;
+        if (a.CU) {
+            const double* src = a.U + (size_t)v * a.ndim;
+            double* dst = a.CU + (size_t)v * a.ndim;
+            for (int k = lane; k < a.ndim; k += kEnsWave) dst[k] = src[k];
+        }
+        if (a.CL && lane == 0) a.CL[v] = a.L[v];
+    }
+}
+
+namespace mcalf {
+const void* ens_kernel_ptr(EnsKernel k) {
+    static const void* const table[] = {(const void*)&mcalf_ens_start_kernel, (const void*)&mcalf_ens_propose_kernel,
+                                        (const void*)&mcalf_ens_decide_kernel};   // in the order of enum EnsKernel
+    static_assert(sizeof(table) / sizeof(table[0]) == kEnsKernelCount, "one entry per EnsKernel");
+    return table[k];
+}
+}  // namespace mcalf

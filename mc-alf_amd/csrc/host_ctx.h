@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -319,6 +319,13 @@ struct mcalf_ctx {
     hipEvent_t ev_ns = nullptr;
     int ns_compact = 0;                     // MCALF_NS_COMPACT / mcalf_set_slice_compact
     mcalf_slice_stats_t ns_stats = {};
+    // The ensemble sampler (host_ens.cpp), grown on demand.  The trial rows [m][ndim] of the moving half, their logL [m], the
+    // Hastings term and ln zeta [2][m] and the inside flags [m] of one half-step; the host-pointer entry's staging (starts,
+    // walkers, logL, transformed rows; status and naccept in ens_hst).  The chain is NOT among them: the host entry releases
+    // it before it returns, the device entry is handed the caller's.
+    enum { kEnY, kEnLY, kEnAux, kEnU0, kEnU, kEnL, kEnTheta, kEnCount };
+    DevBuf<double> enb[kEnCount];
+    DevBuf<int32_t> ens_inside, ens_hst;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).

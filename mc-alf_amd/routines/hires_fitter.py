@@ -592,6 +592,55 @@ class als_fitter:
         res.rows_launched = launched[0]
         return res
 
+    def ensemble_batch(self, U0, nsteps, thin=1, move="stretch", scale=None, seed=0, first_iter=0, chain=True):
+        """(U, theta, logL, status, naccept, chainU, chainL): `nsteps` iterations of an affine-invariant ensemble sampler on
+        the device (`mcalf_ensemble_batch`; HIP kernels).  The rows of U0 (unit cube, [nwalkers, ndim]; nwalkers even, >= 4)
+        are the walkers; the halves [0, n / 2) and [n / 2, n) move in turn, each with partners from the other.  `move`:
+        "stretch" (Goodman & Weare; `scale` = a > 1, None: 2.0) or "de" (differential evolution; `scale` = g > 0, None:
+        2.38 / sqrt(2 ndim)).  The target is `loglike_cube_batch`'s logL with a flat prior over the cube; the integer `ncomp`
+        slot is sampled with it, since the cube transform truncates it.
+
+        theta holds the transformed rows of U and logL[i] is `loglike_cube_batch(U)[i]` bit for bit.  status: 0, or -1 for a
+        walker whose start lies outside the cube or has a NaN (it never moves and comes back as given).  naccept: accepted
+        proposals per walker.  chainU [nsteps // thin, nwalkers, ndim] and chainL [nsteps // thin, nwalkers] hold the state
+        after every thin-th iteration, kept on the device until the call ends (`chain=False`: None, None).  The random words
+        are Philox4x64-10 of (half-step, walker, seed): calling again with the returned U and `first_iter` advanced by
+        `nsteps` is, bit for bit, the longer call."""
+        U0 = self._rows(U0, self.ndim)
+        n = U0.shape[0]
+        moves = {"stretch": _lib.MCALF_ENS_STRETCH, "de": _lib.MCALF_ENS_DE}
+        if move not in moves:
+            raise ValueError(f"move must be 'stretch' or 'de', got {move!r}")
+        if scale is None:
+            scale = 2.0 if move == "stretch" else 2.38 / np.sqrt(2.0 * self.ndim)
+        nsteps, thin = int(nsteps), int(thin)
+        self._ensure_prior()
+        opts = _lib.mcalf_ens_opts(nsteps, thin, moves[move], 0, float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_iter) & 0xFFFFFFFFFFFFFFFF)
+        U, theta = np.empty_like(U0), np.empty_like(U0)
+        logL = np.empty(n)
+        status, naccept = (np.empty(n, dtype=np.int32) for _ in range(2))
+        nkeep = nsteps // thin if chain and nsteps >= 0 and thin >= 1 else 0
+        CU, CL = (np.empty((nkeep, n, self.ndim)), np.empty((nkeep, n))) if chain else (None, None)
+        _lib.check(self._lib.mcalf_ensemble_batch(self._ctx, self._ptr(U0), n, C.addressof(opts), self._ptr(U), self._ptr(theta), self._ptr(logL),
+                                                  status.ctypes.data, naccept.ctypes.data, self._ptr(CU) if chain else None,
+                                                  self._ptr(CL) if chain else None), self._ctx)
+        return U, theta, logL, status, naccept, CU, CL
+
+    def ensemble_sample(self, nwalkers, nsteps, burn=0, thin=1, start=None, ball=None, seed=0, move="stretch", scale=None):
+        """Ensemble MCMC of this problem's posterior with the device's own two entries: `ensemble_batch` for the burn-in and
+        for the kept run (two calls, whatever their length) and `loglike_cube_batch` for the transformed rows of the kept
+        chain (`ensemble.ensemble_sample` keeps the books).  The walkers start uniformly in the cube, or in a ball of
+        half-width `ball` around the cube point `start` (e.g. a `maximize_batch` optimum mapped into the cube).  Returns an
+        `ensemble.EnsembleResult`: the chain in cube and theta coordinates, logL, the acceptance fractions,
+        `autocorr_time()`, and `flat()`, whose output goes into `write_equal_weights`, `model_band_batch` and `eqw_batch`."""
+        from .. import ensemble
+
+        def advance(U0, nsteps, thin=1, seed=0, first_iter=0, chain=True):
+            return self.ensemble_batch(U0, nsteps, thin=thin, move=move, scale=scale, seed=seed, first_iter=first_iter, chain=chain)
+
+        return ensemble.ensemble_sample(lambda U: self.loglike_cube_batch(U), advance, self.ndim, nwalkers, nsteps, burn=burn, thin=thin,
+                                        start=start, ball=ball, seed=seed)
+
     def loglike_hvp_batch(self, P, V, out=None):
         """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's
         `conv_mode` applied to one tangent per row ([batch, ndim] -> [batch, ndim]; HIP kernels, H is never formed).  It is
