@@ -1,14 +1,11 @@
 """Build libmcalf_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is twenty-two translation units: seven device files -- kernels.hip (the likelihood's kernels), grad_kernels.hip
-(the analytic gradient's and the Jacobian products'), eqw_kernels.hip (the equivalent widths'), band_kernels.hip (the posterior
-bands'), fit_kernels.hip (the fit's and the Fisher product's), ns_kernels.hip (nested sampling's replacement step) and ens_kernels.hip (the ensemble
-sampler's moves) -- and the host side of the C ABI --
-host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_config.cpp, host_multi.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_eqw.cpp,
-host_band.cpp, broker.cpp, comm.cpp -- compiled as plain
-C++ against the HIP runtime API.  Objects are
-kept under csrc/obj/ so that an edit of a host file does not recompile the kernels (22 s), and an edit of the gradient's
-device files does not recompile the likelihood's."""
+The library is twenty-three translation units: the seven device files of DEVICE_OBJECTS -- kernels.hip (the likelihood's
+kernels), grad_kernels.hip (the analytic gradient's and the Jacobian products'), eqw_kernels.hip (the equivalent widths'),
+band_kernels.hip (the posterior bands'), fit_kernels.hip (the fit's and the Fisher product's), ns_kernels.hip (nested sampling's
+replacement step) and ens_kernels.hip (the ensemble sampler's moves) -- and the host side of the C ABI, HOST_SOURCES, compiled
+as plain C++ against the HIP runtime API.  Objects are kept under csrc/obj/ so that an edit of a host file does not recompile
+the kernels (22 s), and an edit of one device file does not recompile the others."""
 from __future__ import annotations
 
 import hashlib
@@ -18,30 +15,25 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 KERNEL_SOURCE = "kernels.hip"
-GRAD_SOURCE = "grad_kernels.hip"
-EQW_SOURCE = "eqw_kernels.hip"
-BAND_SOURCE = "band_kernels.hip"
-FIT_SOURCE = "fit_kernels.hip"
-NS_SOURCE = "ns_kernels.hip"
-ENS_SOURCE = "ens_kernels.hip"
-DEVICE_SOURCES = [KERNEL_SOURCE, GRAD_SOURCE, EQW_SOURCE, BAND_SOURCE, FIT_SOURCE, NS_SOURCE, ENS_SOURCE]
-HOST_SOURCES = ["host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp", "host_grad.cpp", "host_fit.cpp", "host_ns.cpp", "host_ens.cpp", "host_eqw.cpp", "host_band.cpp", "broker.cpp", "comm.cpp"]
-SOURCES = DEVICE_SOURCES + HOST_SOURCES
-# what the DEVICE code is made of: the kernel-source hash covers exactly these
+# what the DEVICE code of the likelihood is made of: the kernel-source hash covers exactly these
 HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h"]
-# the gradient's device object (not hashed: the fused kernel does not include these)
-GRAD_DEPS = ["grad_kernels.hip", "grad_args.h", "voigt_grad.h", "kernel_args.h", "voigt_tables.h"]
-# the equivalent widths' device object (its own sources are not hashed either; the Voigt function it shares with the fused kernel,
-# voigt_device.h and voigt_tables.h, is)
-EQW_DEPS = ["eqw_kernels.hip", "eqw_args.h", "voigt_device.h", "kernel_args.h", "voigt_tables.h"]
-# the posterior bands' device object (not hashed: it reads the model rows the fused kernel leaves, and shares no device code with it)
-BAND_DEPS = ["band_kernels.hip", "band_args.h", "kernel_args.h"]
-# the fit's device object (not hashed: per-row linear algebra and a per-pixel multiply, no device code shared with the fused kernel)
-FIT_DEPS = ["fit_kernels.hip", "fit_args.h", "kernel_args.h"]
-# nested sampling's device object (not hashed: a per-row state machine and a counter-based generator, no device code shared with the fused kernel)
-NS_DEPS = ["ns_kernels.hip", "ns_args.h", "kernel_args.h"]
-# the ensemble sampler's device object (not hashed: proposals, an accept rule and the same generator; it shares ns_args.h's constants)
-ENS_DEPS = ["ens_kernels.hip", "ens_args.h", "ns_args.h", "kernel_args.h"]
+# Every device object: its source and the headers it includes.  Only kernels.hip's are hashed: the fused kernel includes none
+# of the others' own files (eqw_kernels.hip shares the hashed Voigt function, voigt_device.h and voigt_tables.h, with it).
+DEVICE_OBJECTS = {
+    KERNEL_SOURCE: HASHED[1:],
+    "grad_kernels.hip": ["grad_args.h", "voigt_grad.h", "kernel_args.h", "voigt_tables.h"],
+    "eqw_kernels.hip": ["eqw_args.h", "voigt_device.h", "kernel_args.h", "voigt_tables.h"],
+    "band_kernels.hip": ["band_args.h", "kernel_args.h"],
+    "fit_kernels.hip": ["fit_args.h", "wave_row.h", "kernel_args.h"],
+    "ns_kernels.hip": ["ns_args.h", "wave_row.h", "kernel_args.h"],
+    "ens_kernels.hip": ["ens_args.h", "wave_row.h", "kernel_args.h"],
+}
+DEVICE_SOURCES = list(DEVICE_OBJECTS)
+# the device files whose kernels' resource usage a verbose build prints (all but the gradient's)
+REPORTED = [s for s in DEVICE_SOURCES if s != "grad_kernels.hip"]
+HOST_SOURCES = ["host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp",
+                "host_staged.cpp", "host_grad.cpp", "host_fit.cpp", "host_ns.cpp", "host_ens.cpp", "host_eqw.cpp", "host_band.cpp", "broker.cpp", "comm.cpp"]
+SOURCES = DEVICE_SOURCES + HOST_SOURCES
 HOST_HEADERS = ["host_ctx.h", "kernel_args.h", "grad_args.h", "eqw_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ens_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
 TARGET = os.path.join(CSRC, "libmcalf_hip.so")
 OBJDIR = os.path.join(CSRC, "obj")
@@ -59,11 +51,7 @@ def _mtime(name: str) -> float:
 
 
 def _deps(src: str):
-    if src == KERNEL_SOURCE:
-        return [src] + HASHED
-    if src in (GRAD_SOURCE, EQW_SOURCE, BAND_SOURCE, FIT_SOURCE, NS_SOURCE, ENS_SOURCE):
-        return {GRAD_SOURCE: GRAD_DEPS, EQW_SOURCE: EQW_DEPS, BAND_SOURCE: BAND_DEPS, FIT_SOURCE: FIT_DEPS, NS_SOURCE: NS_DEPS, ENS_SOURCE: ENS_DEPS}[src]
-    return [src] + HOST_HEADERS
+    return [src] + (DEVICE_OBJECTS[src] if src in DEVICE_OBJECTS else HOST_HEADERS)
 
 
 def _stale(target: str, deps) -> bool:
@@ -122,13 +110,12 @@ def build(force: bool = False, verbose: bool = False, testing: bool = False, tar
             fh.write(stamp)
         relinked = True
     objs.append(kobj)
-    # the gradient's, the equivalent widths', the bands', the fit's, nested sampling's and the ensemble sampler's kernel objects (also
-    # shared by both variants)
-    for dsrc in (GRAD_SOURCE, EQW_SOURCE, BAND_SOURCE, FIT_SOURCE, NS_SOURCE, ENS_SOURCE):
+    # the other device objects (also shared by both variants)
+    for dsrc in DEVICE_SOURCES[1:]:
         dobj = os.path.join(OBJDIR, os.path.splitext(dsrc)[0] + ".o")
         if (force and not testing) or _stale(dobj, _deps(dsrc)):
             cmd = [hipcc] + KERNEL_FLAGS + ["-c", dsrc, "-o", dobj]
-            if verbose and dsrc in (EQW_SOURCE, BAND_SOURCE, FIT_SOURCE, NS_SOURCE, ENS_SOURCE):
+            if verbose and dsrc in REPORTED:
                 cmd.append("-Rpass-analysis=kernel-resource-usage")
             _run(cmd, verbose)
             relinked = True

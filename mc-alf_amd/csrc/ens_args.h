@@ -7,7 +7,6 @@
 #include <cstdint>
 
 #include "kernel_args.h"
-#include "ns_args.h"      // the Philox constants (kPhiloxM0, kPhiloxM1, kPhiloxW0, kPhiloxW1)
 
 namespace mcalf {
 

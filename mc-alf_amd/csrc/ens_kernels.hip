@@ -19,23 +19,11 @@
 
 #pragma clang fp contract(off)
 
+#include "wave_row.h"
+
 using namespace mcalf;
 
 namespace {
-
-// Philox4x64-10 with counter (c0, 0, c2, 0) and key (k0, k1): the four words of the block.
-__device__ __forceinline__ void philox_block(uint64_t c0, uint64_t c2, uint64_t k0, uint64_t k1, uint64_t (&w)[4]) {
-    uint64_t c1 = 0, c3 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t hi0 = __umul64hi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
-        const uint64_t hi1 = __umul64hi(kPhiloxM1, c2), lo1 = kPhiloxM1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += kPhiloxW0; k1 += kPhiloxW1;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
 
 // ln x for normal positive x: the sequence of ens_args.h, operation for operation.
 __device__ __forceinline__ double ens_ln(double x) {
@@ -63,7 +51,7 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_start_kernel(const EnsArgs
     for (int k = lane; k < a.ndim; k += kEnsWave) {
         const double v = a.U0[o + k];
         a.U[o + k] = v;
-        bad |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+        bad |= outside_unit(v);
     }
     const bool outside = __any(bad);
     if (lane != 0) return;
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_propose_kernel(const EnsAr
     double* y = a.Y + (size_t)b * a.ndim;
     const bool moves = __builtin_amdgcn_readfirstlane(a.status[w]) == kEnsOk;
     uint64_t wd[4];
-    philox_block(a.step + 1, (uint64_t)w, a.seed, kEnsKey1, wd);      // (numpy's generator draws at counter + 1)
+    philox4x64_10(a.step + 1, (uint64_t)w, a.seed, kEnsKey1, wd);      // (numpy's generator draws at counter + 1)
     const uint64_t m = (uint64_t)a.m;
     const double xi = (double)(wd[1] >> 11) * 0x1.0p-53;
     const double zeta = (double)((wd[2] >> 11) + 1) * 0x1.0p-53;
@@ -95,7 +83,7 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_propose_kernel(const EnsAr
             const double pj = xj[k];
             const double v = pj + z * (x[k] - pj);
             y[k] = v;
-            out |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+            out |= outside_unit(v);
         }
     } else {
         const uint64_t j1 = wd[0] % m, j2 = (j1 + 1 + wd[3] % (m - 1)) % m;
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_propose_kernel(const EnsAr
         for (int k = lane; k < a.ndim; k += kEnsWave) {
             const double v = x[k] + gamma * (x1[k] - x2[k]);
             y[k] = v;
-            out |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+            out |= outside_unit(v);
         }
     }
     const bool outside = __any(out);

@@ -13,25 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include "fit_args.h"
+#include "wave_row.h"
 
 using namespace mcalf;
 
 namespace {
-
-// Sum over the wave's 64 lanes, the same butterfly every time (every lane gets the result).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// A value every lane already holds with the same bits, as a wave-uniform (scalar) one.
-__device__ __forceinline__ double uniform(double v) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 
 // Active components of a row, as the likelihood decodes the ncomp slot (int() on the numpy path, floor on the JAX path).
 __device__ __forceinline__ int active_count(const FitArgs& a, const double* th) {

@@ -71,52 +71,45 @@ int run_band(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t targonly, 
     a.batch = batch;
     a.npix = (int)npix; a.nstrips = (int)((npix + kBandStrip - 1) / kBandStrip); a.nblocks = (int)nblocks; a.nq = nq;
     for (int j = 0; j < nq; ++j) a.q[j] = q[j];
-    void* args[] = {(void*)&a};
     const dim3 moment_grid((unsigned)((size_t)nblocks * a.nstrips)), pixel_grid((unsigned)((npix + 255) / 256));
-    if (batch > 0) HIP_TRY(ctx, hipLaunchKernel(band_kernel_ptr(kBandSum), moment_grid, dim3(kBandMomentThreads), args, 0, stream));
-    HIP_TRY(ctx, hipLaunchKernel(band_kernel_ptr(kBandMean), pixel_grid, dim3(256), args, 0, stream));
+    if (batch > 0 && (rc = LAUNCH_BLOCK(ctx, band_kernel_ptr(kBandSum), a, moment_grid, dim3(kBandMomentThreads), stream))) return rc;
+    if ((rc = LAUNCH_BLOCK(ctx, band_kernel_ptr(kBandMean), a, pixel_grid, dim3(256), stream))) return rc;
     if (a.var) {
-        if (batch > 0) HIP_TRY(ctx, hipLaunchKernel(band_kernel_ptr(kBandSquares), moment_grid, dim3(kBandMomentThreads), args, 0, stream));
-        HIP_TRY(ctx, hipLaunchKernel(band_kernel_ptr(kBandVar), pixel_grid, dim3(256), args, 0, stream));
+        if (batch > 0 && (rc = LAUNCH_BLOCK(ctx, band_kernel_ptr(kBandSquares), a, moment_grid, dim3(kBandMomentThreads), stream))) return rc;
+        if ((rc = LAUNCH_BLOCK(ctx, band_kernel_ptr(kBandVar), a, pixel_grid, dim3(256), stream))) return rc;
     }
     if (nq > 0) {
-        if (batch > 0) HIP_TRY(ctx, hipLaunchKernel(band_kernel_ptr(kBandSelect), dim3((unsigned)(a.nstrips * nq)), dim3(kBandSelectThreads), args, 0, stream));
-        HIP_TRY(ctx, hipLaunchKernel(band_kernel_ptr(kBandInterp), dim3((unsigned)(((size_t)nq * npix + 255) / 256)), dim3(256), args, 0, stream));
+        if (batch > 0 && (rc = LAUNCH_BLOCK(ctx, band_kernel_ptr(kBandSelect), a, dim3((unsigned)(a.nstrips * nq)), dim3(kBandSelectThreads), stream))) return rc;
+        if ((rc = LAUNCH_BLOCK(ctx, band_kernel_ptr(kBandInterp), a, dim3((unsigned)(((size_t)nq * npix + 255) / 256)), dim3(256), stream))) return rc;
     }
     return MCALF_OK;
 }
 
-int run_host(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t targonly, const double* q, int32_t nq, const BandOuts& o) {
-    if (is_multi(ctx)) {              // all rows have to meet on one device: the first entry's, bit for bit a single-device call
-        mcalf_ctx* sub = ctx->subs[0];
-        ctx->multi_last_active = 1;
-        const int rc = run_host(sub, P, batch, targonly, q, nq, o);
-        return rc ? set_err(ctx, rc, "device entry 0 (HIP device %d): %s", sub->device, sub->err.c_str()) : MCALF_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(P), false);
-    const size_t npix = (size_t)ctx->npix, nP = (size_t)batch * ctx->ndim;
-    DevBuf<double> M;                                     // released when the call returns, on every path
-    if (hipMalloc((void**)&M.p, (size_t)batch * npix * sizeof(double)) != hipSuccess) {
+// The host entry's call: what its device driver needs beyond the columns, and the model matrix, which lives as long as the call.
+struct BandCall { int32_t targonly; const double* q; int32_t nq; DevBuf<double> M; };
+enum { kColP, kColMean, kColVar, kColNvalid, kColQ };
+
+int host_body(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void* arg) {
+    BandCall* c = static_cast<BandCall*>(arg);
+    const size_t npix = (size_t)ctx->npix;
+    if (hipMalloc((void**)&c->M.p, (size_t)rows * npix * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
-        M.p = nullptr;
+        c->M.p = nullptr;
         return set_err(ctx, MCALF_ERR_NOMEM, "mcalf_model_band_batch: no device memory for the %lld x %ld model matrix (%.1f MB); thin the chain",
-                       (long long)batch, ctx->npix, (double)batch * (double)npix * 8e-6);
+                       (long long)rows, ctx->npix, (double)rows * (double)npix * 8e-6);
     }
-    int rc;
-    // staging of the results: mean, var, nvalid, Q[nq]
-    if ((rc = grow_buf(ctx, mcalf_ctx::kBbP, nP)) || (rc = grow_buf(ctx, mcalf_ctx::kBbOut, (3 + (size_t)nq) * npix))) return rc;
-    double* out = ctx->bb[mcalf_ctx::kBbOut];
-    BandOuts d = {o.mean ? out : nullptr, o.var ? out + npix : nullptr, o.Q ? out + 3 * npix : nullptr,
-                  o.nvalid ? reinterpret_cast<int64_t*>(out + 2 * npix) : nullptr};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->bb[mcalf_ctx::kBbP], P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_band(ctx, ctx->bb[mcalf_ctx::kBbP], batch, targonly, q, nq, M, d, ctx->stream))) return rc;
-    if (o.mean) HIP_TRY(ctx, hipMemcpyAsync(o.mean, d.mean, npix * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (o.var) HIP_TRY(ctx, hipMemcpyAsync(o.var, d.var, npix * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (o.nvalid) HIP_TRY(ctx, hipMemcpyAsync(o.nvalid, d.nvalid, npix * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (o.Q) HIP_TRY(ctx, hipMemcpyAsync(o.Q, d.Q, (size_t)nq * npix * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return MCALF_OK;
+    const BandOuts d = {(double*)dev[kColMean], (double*)dev[kColVar], (double*)dev[kColQ], (int64_t*)dev[kColNvalid]};
+    return run_band(ctx, (const double*)dev[kColP], rows, c->targonly, c->q, c->nq, c->M, d, stream);
+}
+
+// All rows have to meet on one device: a multi-device context's first.  The results: mean, var, nvalid, Q[nq].
+int run_host(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t targonly, const double* q, int32_t nq, const BandOuts& o) {
+    BandCall call = {targonly, q, nq, {}};                // (M is released when the call returns, on every path)
+    const size_t d = sizeof(double), npix = (size_t)ctx->npix;
+    StagePlan plan = {{stage_in(P, d, (size_t)ctx->ndim), stage_out(o.mean, d, npix, false), stage_out(o.var, d, npix, false),
+                       stage_out(o.nvalid, sizeof(int64_t), npix, false), stage_out(o.Q, d, (size_t)nq * npix, false)},
+                      5, batch, kStageFirstDevice, kColP, -1, host_body, &call};
+    return run_staged(ctx, plan);
 }
 
 }  // namespace

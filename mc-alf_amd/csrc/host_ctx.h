@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -275,57 +275,54 @@ struct mcalf_ctx {
     DevBuf<double> d_wide, d_wtaps, d_wpartial, d_wrows;
     DevBuf<SampleHdr> d_whdr;
     mcalf_launch_info_t last = {};      // what the last call did (mcalf_last_launch)
+    // The staging arena of the host-pointer analysis entries (host_staged.cpp: run_staged): the device side of a call's arrays,
+    // carved per call in column order.  Nothing in it is alive between calls.
+    DevBuf<char> stage_dev;
     // The derivative entries' device buffers (host_grad.cpp), all grown on demand: the per-row workspaces of one pass -- the
-    // seven every product shares, then the HVP's three -- and the rows of a batch: logL, and the host-pointer entries' staging
-    // (parameters, tangents, gradients or H v, pixel rows).
+    // seven every product shares, then the HVP's three -- and logL of a batch.
     enum { kGbRows, kGbRecs, kGbTaps, kGbDtaps, kGbF, kGbQ, kGbPart, kGbShared, kGbDdtaps = kGbShared, kGbHq, kGbHdq, kGbHvp,
-           kGbLogL = kGbHvp, kGbP, kGbV, kGbG, kGbX, kGbCount };
+           kGbLogL = kGbHvp, kGbCount };
     DevBuf<double> gb[kGbCount];
     // The equivalent-width entries (host_eqw.cpp): the wavelength steps [npix] (hires_fitter.py:485-486; none for a one-pixel
-    // spectrum), the two per-row workspaces of one pass and the host-pointer entry's staging, grown on demand.
+    // spectrum) and the two per-row workspaces of one pass, grown on demand.
     DevBuf<double> d_dlam;
-    enum { kEbRecs, kEbPart, kEbP, kEbWcomp, kEbWblend, kEbCount };
+    enum { kEbRecs, kEbPart, kEbCount };
     DevBuf<double> eb[kEbCount];
     // The posterior-band entries (host_band.cpp), grown on demand: the per-block partials and counts, the per-pixel mean / count
-    // a call keeps for itself when the caller wants neither, the selected order statistics, and the host-pointer entry's staging
-    // (parameter rows in, the 3 + nq per-pixel rows out).  The [batch][npix] model matrix is NOT among them: the host entry
-    // releases it before it returns, the device entry is handed the caller's.
-    enum { kBbPart, kBbMean, kBbCount, kBbSel, kBbP, kBbOut, kBbBufs };
+    // a call keeps for itself when the caller wants neither, and the selected order statistics.  The [batch][npix] model matrix
+    // is NOT among them: the host entry releases it before it returns, the device entry is handed the caller's.
+    enum { kBbPart, kBbMean, kBbCount, kBbSel, kBbBufs };
     DevBuf<double> bb[kBbBufs];
     // The Fisher product and the fit (host_fit.cpp), grown on demand.  d_fitw: W [npix] of the Fisher product, built by its first
     // call (released with the context, after the resident evaluator has left).  kFbDM: the [rows][npix] workspace of one row block
-    // of a Fisher product; the per-row vectors [rows][ndim] and scalars [rows] of one row block of a fit; the host-pointer
-    // entries' staging.  fit_int: status, niter, CG-frozen flag [rows] each and the pins [rows][ndim]; d_fit_live: the counter
-    // of live rows the host entry reads after every outer iteration.
+    // of a Fisher product; the per-row vectors [rows][ndim] and scalars [rows] of one row block of a fit.  fit_int: the CG-frozen
+    // flag [rows] and the pins [rows][ndim]; d_fit_live: the counter of live rows the host entry reads after every outer iteration.
     DevBuf<double> d_fitw;
-    enum { kFbDM, kFbT, kFbG, kFbGT, kFbGu, kFbX, kFbR, kFbPv, kFbV, kFbFV, kFbScal, kFbP0, kFbP, kFbL, kFbHostV, kFbHostFV, kFbCount };
+    enum { kFbDM, kFbT, kFbG, kFbGT, kFbGu, kFbX, kFbR, kFbPv, kFbV, kFbFV, kFbScal, kFbCount };
     DevBuf<double> fb[kFbCount];
-    DevBuf<int32_t> fit_int, fit_hst;       // (fit_hst: the host-pointer entry's status and niter rows)
+    DevBuf<int32_t> fit_int;
     DevBuf<unsigned int> d_fit_live;
     // The nested-sampling replacement primitive (host_ns.cpp), grown on demand.  The trial rows [batch][ndim] the logL launch
-    // evaluates, their logL [batch], the brackets [3][batch] and the direction index [batch] of one call; the host-pointer
-    // entry's staging (starts, points, constraints, direction rows, logL, transformed rows; stream ids; status, nevals and
-    // moves in ns_hst).  d_ns_live: the counter of rows that proposed a trial, which the host entry reads after every step
-    // through the page-locked word h_ns_live.  ns_pack: the step stamps [batch] and, for a call that packs its trial rows
-    // (ns_compact, mcalf_set_slice_compact), their slots and the packed row list [batch] each; kNbYc: the packed trial rows;
-    // ev_ns: recorded behind the copy of the count, so that the host waits for the count and not for the step's logL launch.
+    // evaluates, their logL [batch], the brackets [3][batch] and the direction index [batch] of one call.  d_ns_live: the counter
+    // of rows that proposed a trial, which the host entry reads after every step through the page-locked word h_ns_live.
+    // ns_pack: the step stamps [batch] and, for a call that packs its trial rows (ns_compact, mcalf_set_slice_compact), their
+    // slots and the packed row list [batch] each; kNbYc: the packed trial rows; ev_ns: recorded behind the copy of the count, so
+    // that the host waits for the count and not for the step's logL launch.
     // ns_stats: what the last slice call launched (mcalf_slice_last_stats; a multi-device parent holds the sum over its entries).
-    enum { kNbY, kNbLY, kNbBrk, kNbU0, kNbU, kNbLmin, kNbD, kNbL, kNbTheta, kNbYc, kNbCount };
+    enum { kNbY, kNbLY, kNbBrk, kNbYc, kNbCount };
     DevBuf<double> nb[kNbCount];
-    DevBuf<int32_t> ns_dir, ns_hst, ns_pack;
-    DevBuf<uint64_t> ns_sid;
+    DevBuf<int32_t> ns_dir, ns_pack;
     DevBuf<unsigned int> d_ns_live;
     PinBuf<unsigned int> h_ns_live;
     hipEvent_t ev_ns = nullptr;
     int ns_compact = 0;                     // MCALF_NS_COMPACT / mcalf_set_slice_compact
     mcalf_slice_stats_t ns_stats = {};
     // The ensemble sampler (host_ens.cpp), grown on demand.  The trial rows [m][ndim] of the moving half, their logL [m], the
-    // Hastings term and ln zeta [2][m] and the inside flags [m] of one half-step; the host-pointer entry's staging (starts,
-    // walkers, logL, transformed rows; status and naccept in ens_hst).  The chain is NOT among them: the host entry releases
-    // it before it returns, the device entry is handed the caller's.
-    enum { kEnY, kEnLY, kEnAux, kEnU0, kEnU, kEnL, kEnTheta, kEnCount };
+    // Hastings term and ln zeta [2][m] and the inside flags [m] of one half-step.  The chain is NOT among them: the host entry
+    // releases it before it returns, the device entry is handed the caller's.
+    enum { kEnY, kEnLY, kEnAux, kEnCount };
     DevBuf<double> enb[kEnCount];
-    DevBuf<int32_t> ens_inside, ens_hst;
+    DevBuf<int32_t> ens_inside;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -355,6 +352,17 @@ template <typename T> inline int grow(mcalf_ctx* ctx, DevBuf<T>& buf, size_t nee
     buf.cap = need_elems;
     return MCALF_OK;
 }
+
+// The launch of a kernel that takes ONE argument block by value.  `expr` is what a failure names, as HIP_TRY would have named
+// the call; LAUNCH_BLOCK writes it from the call's own expressions.
+template <typename T>
+inline int launch_block(mcalf_ctx* ctx, const void* kernel, const T& args, dim3 grid, dim3 block, hipStream_t stream, const char* expr) {
+    void* argv[] = {(void*)&args};
+    const hipError_t e = hipLaunchKernel(kernel, grid, block, argv, 0, stream);
+    return e == hipSuccess ? MCALF_OK : set_err(ctx, MCALF_ERR_HIP, "%s failed: %s", expr, hipGetErrorString(e));
+}
+#define LAUNCH_BLOCK(ctx, kernel, a, grid, block, stream) \
+    launch_block(ctx, kernel, a, grid, block, stream, "hipLaunchKernel(" #kernel ", " #grid ", " #block ", args, 0, " #stream ")")
 
 inline double now_us() {
     timespec ts;
@@ -422,6 +430,10 @@ int launch(mcalf_ctx* ctx, const LaunchReq& q);        // enqueue one batch on q
 // Rows [row0, row0 + nrows) of the batch on `stream` (a row block has a stream of its own): set-up, fused kernel, finalize when tiled.
 int launch_range(mcalf_ctx* ctx, const LaunchReq& q, int64_t row0, int64_t nrows, int chunk, hipStream_t stream, bool timed_ok,
                  int wide_stage = kWideNone);
+// What the cube samplers (host_ns.cpp, host_ens.cpp) put around their own kernels: logL of the `n` unit-cube rows at Y into LY,
+// exactly what mcalf_loglike_cube_batch_device(Y) writes; the transformed rows of U, as that launch forms them.
+int cube_logl(mcalf_ctx* ctx, const double* Y, const double* LY, int64_t n, hipStream_t stream);
+int cube_to_theta(mcalf_ctx* ctx, const double* U, double* theta, int64_t n, hipStream_t stream);
 int launch_preflight(mcalf_ctx* ctx, int mode, int64_t batch);   // what can fail WITHOUT anything having been enqueued
 int launch_finalize(mcalf_ctx* ctx, const KArgs& a, int64_t nrows, int mode, hipStream_t stream, int nparts = 0, bool signal = false);
 int grow_sample_ws(mcalf_ctx* ctx, int64_t batch);     // the per-live-point workspaces of the set-up kernel
@@ -453,6 +465,31 @@ inline void multi_bounds(int64_t batch, int n, int k, int64_t* lo, int64_t* hi) 
 int multi_active(const mcalf_ctx* ctx, int64_t batch);  // sub-contexts a batch of this size is cut over (>= 1)
 // fn(sub, k, lo, hi) on every active sub-context concurrently (sub 0 on the calling thread); first error wins.
 int multi_run(mcalf_ctx* ctx, int64_t batch, WorkFn fn, void* arg);      // (fn's `who` is the sub-context)
+
+// ---- host_staged.cpp: the staged call of the host-pointer analysis entries ----------------------------------------------
+// One array of a call.  `count`: elements per row for an array that is cut with the rows (`rows`), else elements in all.
+// `own`: the body supplies the device side itself (a workspace, an allocation of the call) by setting its dev[] slot; the
+// arena reserves nothing for it.  An array that is not `present` (an optional output the caller left NULL) has dev[] NULL.
+struct StageCol { void* host; size_t elem, count; bool rows, out, present, own; };
+inline StageCol stage_in(const void* host, size_t elem, size_t count, bool rows = true) {
+    return {const_cast<void*>(host), elem, count, rows, false, host != nullptr, false};
+}
+inline StageCol stage_out(void* host, size_t elem, size_t count, bool rows = true, bool own = false) {
+    return {host, elem, count, rows, true, host != nullptr, own};
+}
+constexpr int kStageMaxCols = 12;
+enum StageShard { kStageCutRows, kStageFirstDevice };    // a multi-device context: the rows over its devices / all on its first
+// The entry's device driver over `rows` rows of (sub-)context `ctx` on `stream`; dev[i] is the device side of column i.
+typedef int (*StageBody)(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void* arg);
+struct StagePlan {
+    StageCol cols[kStageMaxCols]; int ncols;
+    int64_t batch; StageShard shard;
+    int pin_in, pin_out;          // the columns whose page-lockedness the launch record reports (-1: none, reported as 0)
+    StageBody body; void* arg;
+};
+// shard, hipSetDevice, begin_call(MCALF_PATH_HOST_STAGED), the arena, the inputs to the device in column order, the body, the
+// outputs back in column order, hipStreamSynchronize -- all on the context's stream.
+int run_staged(mcalf_ctx* ctx, const StagePlan& plan);
 
 // ---- host_stream.cpp: ONE streaming launch for a large host-pointer batch ----------------------------------------------
 int stream_probe_xcds(mcalf_ctx* ctx);                 // which XCDs the context's stream reaches (ctx->xcd_mask)

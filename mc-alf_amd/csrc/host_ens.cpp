@@ -55,18 +55,8 @@ int ens_check(mcalf_ctx* ctx, const char* name, const EnsRows& r, int64_t n, con
     return MCALF_OK;
 }
 
-int launch_ens(mcalf_ctx* ctx, EnsKernel k, const EnsArgs& a, hipStream_t stream, unsigned grid) {
-    void* args[] = {(void*)&a};
-    HIP_TRY(ctx, hipLaunchKernel(ens_kernel_ptr(k), dim3(grid), dim3(kEnsWave), args, 0, stream));
-    return MCALF_OK;
-}
-
-// logL of the `n` rows at Y into LY, exactly what mcalf_loglike_cube_batch_device(Y) writes.
-int trial_logl(mcalf_ctx* ctx, const double* Y, const double* LY, int64_t n, hipStream_t stream) {
-    LaunchReq q(kModeLogL, Y, n, stream);
-    q.d_out = const_cast<double*>(LY); q.from_cube = true;
-    return launch(ctx, q);
-}
+// What a failed launch of a kernel of ens_kernels.hip is reported as.
+constexpr char kEnsLaunch[] = "hipLaunchKernel(ens_kernel_ptr(k), dim3(grid), dim3(kEnsWave), args, 0, stream)";
 
 // The call over `n` device rows on `stream`: issued in one go, nothing is read back.
 int run_ens(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_ens_opts& o, hipStream_t stream) {
@@ -80,7 +70,8 @@ int run_ens(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_ens_opts& o
     a.U0 = r.U0; a.U = r.U; a.L = r.logL; a.status = r.status; a.naccept = r.naccept;
     a.Y = ctx->enb[mcalf_ctx::kEnY]; a.LY = ctx->enb[mcalf_ctx::kEnLY]; a.aux = ctx->enb[mcalf_ctx::kEnAux]; a.inside = ctx->ens_inside;
     a.seed = o.seed; a.scale = o.scale; a.n = (int)n; a.m = (int)m; a.ndim = ctx->ndim; a.move = o.move;
-    if ((rc = launch_ens(ctx, kEnsStart, a, stream, (unsigned)n)) || (rc = trial_logl(ctx, a.U, a.L, n, stream))) return rc;
+    const dim3 all((unsigned)n), half((unsigned)m), wave(kEnsWave);
+    if ((rc = launch_block(ctx, ens_kernel_ptr(kEnsStart), a, all, wave, stream, kEnsLaunch)) || (rc = cube_logl(ctx, a.U, a.L, n, stream))) return rc;
     const size_t slotU = nb * ndim;
     for (int i = 0; i < o.nsteps; ++i) {
         const bool keep = (i + 1) % o.thin == 0;
@@ -90,59 +81,48 @@ int run_ens(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_ens_opts& o
             a.keep = keep && h == 1 && (r.CU || r.CL) ? 1 : 0;
             a.CU = a.keep && r.CU ? r.CU + slot * slotU : nullptr;
             a.CL = a.keep && r.CL ? r.CL + slot * nb : nullptr;
-            if ((rc = launch_ens(ctx, kEnsPropose, a, stream, (unsigned)m)) || (rc = trial_logl(ctx, a.Y, a.LY, (int64_t)m, stream)) ||
-                (rc = launch_ens(ctx, kEnsDecide, a, stream, (unsigned)m)))
+            if ((rc = launch_block(ctx, ens_kernel_ptr(kEnsPropose), a, half, wave, stream, kEnsLaunch)) || (rc = cube_logl(ctx, a.Y, a.LY, (int64_t)m, stream)) ||
+                (rc = launch_block(ctx, ens_kernel_ptr(kEnsDecide), a, half, wave, stream, kEnsLaunch)))
                 return rc;
         }
     }
-    if (r.theta) {                                      // the transformed rows of the walkers, as the cube launch forms them
-        const double *lo = ctx->d_prior, *hi = ctx->d_prior + ndim, *cube = r.U;
-        long total = (long)(nb * ndim);
-        int nd = ctx->ndim, slot = ctx->startind, as_int = ctx->prior_int;
-        double* theta = r.theta;
-        void* kargs[] = {(void*)&lo, (void*)&hi, (void*)&cube, (void*)&total, (void*)&nd, (void*)&slot, (void*)&as_int, (void*)&theta};
-        HIP_TRY(ctx, hipLaunchKernel(scale_cube_kernel_ptr(), dim3((unsigned)((total + 255) / 256)), dim3(256), kargs, 0, stream));
-    }
+    if (r.theta) return cube_to_theta(ctx, r.U, r.theta, n, stream);      // the transformed rows of the walkers
     return MCALF_OK;
 }
 
-int ens_host(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_ens_opts& o) {
-    if (is_multi(ctx)) {              // the walkers have to meet on one device: the first entry's, bit for bit a single-device call
-        mcalf_ctx* sub = ctx->subs[0];
-        ctx->multi_last_active = 1;
-        const int rc = ens_host(sub, r, n, o);
-        return rc ? set_err(ctx, rc, "device entry 0 (HIP device %d): %s", sub->device, sub->err.c_str()) : MCALF_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(r.U0), is_pinned_host(r.U));
-    const size_t nb = (size_t)n, nu = nb * ctx->ndim, nkeep = (size_t)(o.nsteps / o.thin);
-    DevBuf<double>* b = ctx->enb;
-    int rc;
-    if ((rc = grow(ctx, b[mcalf_ctx::kEnU0], nu)) || (rc = grow(ctx, b[mcalf_ctx::kEnU], nu)) || (rc = grow(ctx, b[mcalf_ctx::kEnL], nb)) ||
-        (r.theta && (rc = grow(ctx, b[mcalf_ctx::kEnTheta], nu))) || (rc = grow(ctx, ctx->ens_hst, 2 * nb)))
-        return rc;
-    DevBuf<double> chain;                                 // released when the call returns, on every path
-    const size_t nCU = r.CU ? nkeep * nu : 0, nCL = r.CL ? nkeep * nb : 0;
-    if (nCU + nCL > 0 && hipMalloc((void**)&chain.p, (nCU + nCL) * sizeof(double)) != hipSuccess) {
+// The host entry's call: the options, the chain arrays the caller wants, and the chain itself (the CU slots, then the CL slots),
+// which lives as long as the call.
+struct EnsCall { const mcalf_ens_opts* o; size_t nCU, nCL; DevBuf<double> chain; };
+enum EnsCol { kColU0, kColU, kColTheta, kColL, kColStatus, kColNaccept, kColCU, kColCL, kEnsCols };
+
+// The host entry's device driver (host_staged.cpp: run_staged); columns in the order of EnsCol, the chain's two its own.
+int ens_body(mcalf_ctx* ctx, void** dev, int64_t n, hipStream_t stream, void* arg) {
+    EnsCall* c = static_cast<EnsCall*>(arg);
+    if (c->nCU + c->nCL > 0 && hipMalloc((void**)&c->chain.p, (c->nCU + c->nCL) * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
-        chain.p = nullptr;
+        c->chain.p = nullptr;
         return set_err(ctx, MCALF_ERR_NOMEM, "mcalf_ensemble_batch: no device memory for the chain of %zu slots (%.1f MB); raise thin",
-                       nkeep, (double)(nCU + nCL) * 8e-6);
+                       (size_t)(c->o->nsteps / c->o->thin), (double)(c->nCU + c->nCL) * 8e-6);
     }
-    const EnsRows d = {b[mcalf_ctx::kEnU0], b[mcalf_ctx::kEnU], r.theta ? b[mcalf_ctx::kEnTheta].p : nullptr, b[mcalf_ctx::kEnL],
-                       ctx->ens_hst, ctx->ens_hst + nb, nCU ? chain.p : nullptr, nCL ? chain.p + nCU : nullptr};
-    const hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kEnU0], r.U0, nu * sizeof(double), hipMemcpyHostToDevice, st));
-    if ((rc = run_ens(ctx, d, n, o, st))) { (void)hipStreamSynchronize(st); return rc; }      // (the chain is freed behind the stream)
-    HIP_TRY(ctx, hipMemcpyAsync(r.U, d.U, nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (r.theta) HIP_TRY(ctx, hipMemcpyAsync(r.theta, d.theta, nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.logL, d.logL, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.status, d.status, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.naccept, d.naccept, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (nCU) HIP_TRY(ctx, hipMemcpyAsync(r.CU, d.CU, nCU * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (nCL) HIP_TRY(ctx, hipMemcpyAsync(r.CL, d.CL, nCL * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MCALF_OK;
+    dev[kColCU] = c->nCU ? c->chain.p : nullptr;
+    dev[kColCL] = c->nCL ? c->chain.p + c->nCU : nullptr;
+    const EnsRows d = {(const double*)dev[kColU0], (double*)dev[kColU], (double*)dev[kColTheta], (double*)dev[kColL], (int32_t*)dev[kColStatus],
+                       (int32_t*)dev[kColNaccept], (double*)dev[kColCU], (double*)dev[kColCL]};
+    const int rc = run_ens(ctx, d, n, *c->o, stream);
+    if (rc) (void)hipStreamSynchronize(stream);           // (the chain is freed behind the stream)
+    return rc;
+}
+
+// The walkers have to meet on one device: a multi-device context's first.
+int ens_host(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_ens_opts& o) {
+    const size_t d = sizeof(double), i = sizeof(int32_t), ndim = (size_t)ctx->ndim, nkeep = (size_t)(o.nsteps / o.thin);
+    EnsCall call = {&o, r.CU ? nkeep * (size_t)n * ndim : 0, r.CL ? nkeep * (size_t)n : 0, {}};      // (the chain is released when the call returns)
+    StagePlan plan = {{stage_in(r.U0, d, ndim), stage_out(r.U, d, ndim), stage_out(r.theta, d, ndim), stage_out(r.logL, d, 1), stage_out(r.status, i, 1),
+                       stage_out(r.naccept, i, 1), stage_out(r.CU, d, call.nCU, false, true), stage_out(r.CL, d, call.nCL, false, true)},
+                      kEnsCols, n, kStageFirstDevice, kColU0, kColU, ens_body, &call};
+    plan.cols[kColCU].present = call.nCU > 0;             // (a call that keeps no slot has no chain)
+    plan.cols[kColCL].present = call.nCL > 0;
+    return run_staged(ctx, plan);
 }
 
 }  // namespace

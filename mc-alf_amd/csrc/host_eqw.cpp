@@ -60,39 +60,25 @@ int run_eqw(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, d
         a.Wcomp = dWcomp ? dWcomp + (size_t)row0 * nrec : nullptr;
         a.Wblend = dWblend ? dWblend + (size_t)row0 * ctx->nlines : nullptr;
         a.nrows = (int)std::min(chunk, batch - row0);
-        void* args[] = {(void*)&a};
-        HIP_TRY(ctx, hipLaunchKernel(eqw_kernel_ptr(kEqwSetup), dim3((unsigned)a.nrows), dim3(64), args, 0, stream));
-        HIP_TRY(ctx, hipLaunchKernel(eqw_kernel_ptr(kEqwPixel), dim3((unsigned)a.ntiles, (unsigned)a.nrows), dim3(kEqwBlock), args, 0, stream));
-        HIP_TRY(ctx, hipLaunchKernel(eqw_kernel_ptr(kEqwFinalize), dim3((unsigned)(((size_t)a.nrows * ncells + 255) / 256)), dim3(256), args, 0, stream));
+        if ((rc = LAUNCH_BLOCK(ctx, eqw_kernel_ptr(kEqwSetup), a, dim3((unsigned)a.nrows), dim3(64), stream)) ||
+            (rc = LAUNCH_BLOCK(ctx, eqw_kernel_ptr(kEqwPixel), a, dim3((unsigned)a.ntiles, (unsigned)a.nrows), dim3(kEqwBlock), stream)) ||
+            (rc = LAUNCH_BLOCK(ctx, eqw_kernel_ptr(kEqwFinalize), a, dim3((unsigned)(((size_t)a.nrows * ncells + 255) / 256)), dim3(256), stream)))
+            return rc;
     }
     return MCALF_OK;
 }
 
-struct HostShard { const double* P; int32_t indexing; double *Wcomp, *Wblend; int64_t ndim, nrec, nlines; };
+// The host entry's device driver (host_staged.cpp: run_staged); columns P, Wcomp, Wblend.
+int host_body(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void* arg) {
+    return run_eqw(ctx, (const double*)dev[0], rows, *static_cast<const int32_t*>(arg), (double*)dev[1], (double*)dev[2], stream);
+}
 
 int run_host(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t indexing, double* Wcomp, double* Wblend) {
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
-        HostShard c = {P, indexing, Wcomp, Wblend, ctx->ndim, eqw_nrec(ctx), ctx->nlines};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const HostShard* s = static_cast<const HostShard*>(arg);
-            return run_host(static_cast<mcalf_ctx*>(sub), s->P + (size_t)lo * s->ndim, hi - lo, s->indexing,
-                            s->Wcomp ? s->Wcomp + (size_t)lo * s->nrec : nullptr, s->Wblend ? s->Wblend + (size_t)lo * s->nlines : nullptr);
-        }, &c);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(P), is_pinned_host(Wcomp ? Wcomp : Wblend));
-    const size_t nP = (size_t)batch * ctx->ndim, nC = Wcomp ? (size_t)batch * (size_t)eqw_nrec(ctx) : 0, nB = Wblend ? (size_t)batch * ctx->nlines : 0;
-    int rc;
-    if ((rc = grow_buf(ctx, mcalf_ctx::kEbP, nP)) || (rc = grow_buf(ctx, mcalf_ctx::kEbWcomp, nC)) || (rc = grow_buf(ctx, mcalf_ctx::kEbWblend, nB))) return rc;
-    const DevBuf<double>* eb = ctx->eb;
-    double* dC = nC ? eb[mcalf_ctx::kEbWcomp].p : nullptr;
-    double* dB = Wblend ? eb[mcalf_ctx::kEbWblend].p : nullptr;
-    HIP_TRY(ctx, hipMemcpyAsync(eb[mcalf_ctx::kEbP], P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_eqw(ctx, eb[mcalf_ctx::kEbP], batch, indexing, dC, dB, ctx->stream))) return rc;
-    if (nC) HIP_TRY(ctx, hipMemcpyAsync(Wcomp, dC, nC * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (nB) HIP_TRY(ctx, hipMemcpyAsync(Wblend, dB, nB * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return MCALF_OK;
+    const size_t d = sizeof(double), nrec = (size_t)eqw_nrec(ctx);
+    StagePlan plan = {{stage_in(P, d, (size_t)ctx->ndim), stage_out(Wcomp, d, nrec), stage_out(Wblend, d, (size_t)ctx->nlines)},
+                      3, batch, kStageCutRows, 0, Wcomp ? 1 : 2, host_body, &indexing};
+    plan.cols[1].present = Wcomp && nrec;                 // (a layout without components has no Wcomp rows)
+    return run_staged(ctx, plan);
 }
 
 }  // namespace

@@ -40,13 +40,10 @@ int ensure_w(mcalf_ctx* ctx) {
 }
 
 int launch_fit(mcalf_ctx* ctx, FitKernel k, const FitArgs& a, hipStream_t stream) {
-    void* args[] = {(void*)&a};
     if (k == kFitWeight)
-        HIP_TRY(ctx, hipLaunchKernel(fit_kernel_ptr(k), dim3((unsigned)((a.npix + kFitPixBlock - 1) / kFitPixBlock), (unsigned)a.nrows),
-                                     dim3(kFitPixBlock), args, 0, stream));
-    else
-        HIP_TRY(ctx, hipLaunchKernel(fit_kernel_ptr(k), dim3((unsigned)a.nrows), dim3(kFitWave), args, 0, stream));
-    return MCALF_OK;
+        return LAUNCH_BLOCK(ctx, fit_kernel_ptr(k), a, dim3((unsigned)((a.npix + kFitPixBlock - 1) / kFitPixBlock), (unsigned)a.nrows),
+                            dim3(kFitPixBlock), stream);
+    return LAUNCH_BLOCK(ctx, fit_kernel_ptr(k), a, dim3((unsigned)a.nrows), dim3(kFitWave), stream);
 }
 
 // FV = J^T W J V over `n` <= fit_max_rows device rows: the JVP into the workspace, the weight, the VJP of the workspace.
@@ -86,30 +83,15 @@ int fisher_check(mcalf_ctx* ctx, const char* name, const double* P, const double
     return MCALF_OK;
 }
 
-struct FisherShard { const double *P, *V; double* FV; int64_t ndim; };
+// The host entry's device driver (host_staged.cpp: run_staged); columns P, V, FV.
+int fisher_body(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void*) {
+    return run_fisher(ctx, (const double*)dev[0], (const double*)dev[1], rows, (double*)dev[2], stream);
+}
 
 int fisher_host(mcalf_ctx* ctx, const double* P, const double* V, int64_t batch, double* FV) {
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's array
-        FisherShard c = {P, V, FV, ctx->ndim};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const FisherShard* s = static_cast<const FisherShard*>(arg);
-            const size_t o = (size_t)lo * s->ndim;
-            return fisher_host(static_cast<mcalf_ctx*>(sub), s->P + o, s->V + o, hi - lo, s->FV + o);
-        }, &c);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(P), is_pinned_host(FV));
-    const size_t n = (size_t)batch * ctx->ndim;
-    int rc;
-    if ((rc = grow_buf(ctx, mcalf_ctx::kFbP0, n)) || (rc = grow_buf(ctx, mcalf_ctx::kFbHostV, n)) || (rc = grow_buf(ctx, mcalf_ctx::kFbHostFV, n)))
-        return rc;
-    const DevBuf<double>* fb = ctx->fb;
-    HIP_TRY(ctx, hipMemcpyAsync(fb[mcalf_ctx::kFbP0], P, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(fb[mcalf_ctx::kFbHostV], V, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_fisher(ctx, fb[mcalf_ctx::kFbP0], fb[mcalf_ctx::kFbHostV], batch, fb[mcalf_ctx::kFbHostFV], ctx->stream))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(FV, fb[mcalf_ctx::kFbHostFV], n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return MCALF_OK;
+    const size_t d = sizeof(double), ndim = (size_t)ctx->ndim;
+    StagePlan plan = {{stage_in(P, d, ndim), stage_in(V, d, ndim), stage_out(FV, d, ndim)}, 3, batch, kStageCutRows, 0, 2, fisher_body, nullptr};
+    return run_staged(ctx, plan);
 }
 
 // ---- the fit ---------------------------------------------------------------------------------------------------------------
@@ -193,34 +175,17 @@ int run_fit(mcalf_ctx* ctx, const FitRows& r, int64_t batch, const mcalf_fit_opt
     return MCALF_OK;
 }
 
-struct FitShard { FitRows r; const mcalf_fit_opts* o; int64_t ndim; };
+// The host entry's device driver (host_staged.cpp: run_staged); columns P0, P, logL, status, niter.
+int fit_body(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void* arg) {
+    const FitRows d = {(const double*)dev[0], (double*)dev[1], (double*)dev[2], (int32_t*)dev[3], (int32_t*)dev[4]};
+    return run_fit(ctx, d, rows, *static_cast<const mcalf_fit_opts*>(arg), stream, true);
+}
 
 int fit_host(mcalf_ctx* ctx, const FitRows& r, int64_t batch, const mcalf_fit_opts& o) {
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
-        FitShard c = {r, &o, ctx->ndim};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const FitShard* s = static_cast<const FitShard*>(arg);
-            const size_t o0 = (size_t)lo * s->ndim;
-            const FitRows part = {s->r.P0 + o0, s->r.P + o0, s->r.logL + lo, s->r.status + lo, s->r.niter + lo};
-            return fit_host(static_cast<mcalf_ctx*>(sub), part, hi - lo, *s->o);
-        }, &c);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(r.P0), is_pinned_host(r.P));
-    const size_t nb = (size_t)batch, n = nb * ctx->ndim;
-    int rc;
-    if ((rc = grow_buf(ctx, mcalf_ctx::kFbP0, n)) || (rc = grow_buf(ctx, mcalf_ctx::kFbP, n)) || (rc = grow_buf(ctx, mcalf_ctx::kFbL, nb)) ||
-        (rc = grow(ctx, ctx->fit_hst, 2 * nb)))
-        return rc;
-    const FitRows d = {ctx->fb[mcalf_ctx::kFbP0], ctx->fb[mcalf_ctx::kFbP], ctx->fb[mcalf_ctx::kFbL], ctx->fit_hst, ctx->fit_hst + nb};
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->fb[mcalf_ctx::kFbP0], r.P0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_fit(ctx, d, batch, o, ctx->stream, true))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(r.P, d.P, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(r.logL, d.logL, nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(r.status, d.status, nb * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(r.niter, d.niter, nb * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return MCALF_OK;
+    const size_t d = sizeof(double), i = sizeof(int32_t), ndim = (size_t)ctx->ndim;
+    StagePlan plan = {{stage_in(r.P0, d, ndim), stage_out(r.P, d, ndim), stage_out(r.logL, d, 1), stage_out(r.status, i, 1), stage_out(r.niter, i, 1)},
+                      5, batch, kStageCutRows, 0, 1, fit_body, const_cast<mcalf_fit_opts*>(&o)};
+    return run_staged(ctx, plan);
 }
 
 }  // namespace

@@ -3,7 +3,7 @@
 // workspaces, whether logL comes first, its kernel sequence, its row pointers -- and ONE driver (run_product) runs any of
 // them pass by pass over row blocks whose per-row workspaces stay within kGradChunkBytes.  logL itself comes from the
 // likelihood's own launch (host_launch.cpp: launch), so the entries agree on it bit for bit.  ONE helper serves the
-// host-pointer entries (run_host: staging, multi-device split) and one the device-pointer entries (run_device).
+// host-pointer entries (run_host: the staged call of host_staged.cpp) and one the device-pointer entries (run_device).
 #include <cmath>
 
 #include "grad_args.h"
@@ -111,10 +111,8 @@ int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStre
         a.P = c.P + (size_t)row0 * ctx->ndim;
         a.nrows = (int)std::min(chunk, batch - row0);
         p.bind(a, c, (size_t)row0 * ctx->ndim, (size_t)row0 * ctx->npix, row0);
-        for (const GradKernel* k = p.seq; *k != kGradKernelCount; ++k) {
-            void* args[] = {(void*)&a};
-            HIP_TRY(ctx, hipLaunchKernel(grad_kernel_ptr(*k), grad_grid(*k, a), dim3(kGradBlock), args, 0, stream));
-        }
+        for (const GradKernel* k = p.seq; *k != kGradKernelCount; ++k)
+            if ((rc = LAUNCH_BLOCK(ctx, grad_kernel_ptr(*k), a, grad_grid(*k, a), dim3(kGradBlock), stream))) return rc;
     }
     return MCALF_OK;
 }
@@ -130,36 +128,24 @@ int run_device(mcalf_ctx* ctx, const Product& p, const Call& c, int64_t batch, v
     return run_product(ctx, p, c, batch, (hipStream_t)stream);
 }
 
-// A host-pointer entry: P and X to the device, the product, Y (and logL where the caller wants it: L may be NULL) back, all on
-// the context's stream; a multi-device context cuts the rows over its devices.
-struct HostShard { const Product* p; const double *P, *X; double *Y, *L; int64_t ndim, xw, yw; };
+// A host-pointer entry: P and X to the device, the product, Y (and logL where the caller wants it: L may be NULL) back -- the
+// staged call of host_staged.cpp, rows cut over the devices.  logL comes from the product's own buffer.
+enum { kColP, kColX, kColY, kColL };
+
+int host_body(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void* arg) {
+    const int rc = run_product(ctx, *static_cast<const Product*>(arg), {(const double*)dev[kColP], (const double*)dev[kColX], (double*)dev[kColY], nullptr},
+                               rows, stream);
+    dev[kColL] = ctx->gb[mcalf_ctx::kGbLogL];
+    return rc;
+}
 
 int run_host(mcalf_ctx* ctx, const Product& p, const double* P, const double* X, int64_t batch, double* Y, double* L) {
     if (!ctx || batch < 0 || (batch > 0 && (!P || !Y || (p.has_x && !X)))) return set_err(ctx, MCALF_ERR_INVALID, "NULL argument");
     if (batch == 0) return MCALF_OK;
-    const int64_t xw = p.x_pix ? ctx->npix : ctx->ndim, yw = p.y_pix ? ctx->npix : ctx->ndim;
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
-        HostShard c = {&p, P, X, Y, L, ctx->ndim, xw, yw};
-        return multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const HostShard* s = static_cast<const HostShard*>(arg);
-            return run_host(static_cast<mcalf_ctx*>(sub), *s->p, s->P + (size_t)lo * s->ndim, s->X ? s->X + (size_t)lo * s->xw : nullptr,
-                            hi - lo, s->Y + (size_t)lo * s->yw, s->L ? s->L + lo : nullptr);
-        }, &c);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(P), is_pinned_host(Y));   // H2D, launch, D2H on the context's stream
-    const int bX = p.x_pix ? mcalf_ctx::kGbX : mcalf_ctx::kGbV, bY = p.y_pix ? mcalf_ctx::kGbX : mcalf_ctx::kGbG;
-    const size_t nP = (size_t)batch * ctx->ndim, nX = p.has_x ? (size_t)batch * xw : 0, nY = (size_t)batch * yw;
-    int rc;
-    if ((rc = grow_buf(ctx, mcalf_ctx::kGbP, nP)) || (rc = grow_buf(ctx, bX, nX)) || (rc = grow_buf(ctx, bY, nY))) return rc;
-    const DevBuf<double>* gb = ctx->gb;
-    HIP_TRY(ctx, hipMemcpyAsync(gb[mcalf_ctx::kGbP], P, nP * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (p.has_x) HIP_TRY(ctx, hipMemcpyAsync(gb[bX], X, nX * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = run_product(ctx, p, {gb[mcalf_ctx::kGbP], p.has_x ? gb[bX].p : nullptr, gb[bY], nullptr}, batch, ctx->stream))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(Y, gb[bY], nY * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (L) HIP_TRY(ctx, hipMemcpyAsync(L, gb[mcalf_ctx::kGbLogL], (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return MCALF_OK;
+    const size_t d = sizeof(double), ndim = (size_t)ctx->ndim, npix = (size_t)ctx->npix;
+    StagePlan plan = {{stage_in(P, d, ndim), stage_in(p.has_x ? X : nullptr, d, p.x_pix ? npix : ndim), stage_out(Y, d, p.y_pix ? npix : ndim),
+                       stage_out(L, d, 1, true, true)}, 4, batch, kStageCutRows, kColP, kColY, host_body, const_cast<Product*>(&p)};
+    return run_staged(ctx, plan);
 }
 
 }  // namespace

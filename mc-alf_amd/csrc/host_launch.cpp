@@ -211,3 +211,20 @@ int launch(mcalf_ctx* ctx, const LaunchReq& q) {
     for (int c = 1; c < nchunks; ++c) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->ev_join[c - 1], 0));
     return MCALF_OK;
 }
+
+// logL of the `n` unit-cube rows at Y into LY, exactly what mcalf_loglike_cube_batch_device(Y) writes.
+int cube_logl(mcalf_ctx* ctx, const double* Y, const double* LY, int64_t n, hipStream_t stream) {
+    LaunchReq q(kModeLogL, Y, n, stream);
+    q.d_out = const_cast<double*>(LY); q.from_cube = true;
+    return launch(ctx, q);
+}
+
+// The transformed rows of the `n` unit-cube rows at U, as the cube launch forms them.
+int cube_to_theta(mcalf_ctx* ctx, const double* U, double* theta, int64_t n, hipStream_t stream) {
+    const double *lo = ctx->d_prior, *hi = ctx->d_prior + ctx->ndim, *cube = U;
+    long total = (long)((size_t)n * (size_t)ctx->ndim);
+    int nd = ctx->ndim, slot = ctx->startind, as_int = ctx->prior_int;
+    void* kargs[] = {(void*)&lo, (void*)&hi, (void*)&cube, (void*)&total, (void*)&nd, (void*)&slot, (void*)&as_int, (void*)&theta};
+    HIP_TRY(ctx, hipLaunchKernel(scale_cube_kernel_ptr(), dim3((unsigned)((total + 255) / 256)), dim3(256), kargs, 0, stream));
+    return MCALF_OK;
+}

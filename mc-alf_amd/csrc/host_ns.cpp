@@ -42,18 +42,8 @@ int ns_check(mcalf_ctx* ctx, const char* name, const NsRows& r, int64_t batch, c
     return MCALF_OK;
 }
 
-int launch_ns(mcalf_ctx* ctx, NsKernel k, const NsArgs& a, hipStream_t stream, unsigned grid, unsigned block = kNsWave) {
-    void* args[] = {(void*)&a};
-    HIP_TRY(ctx, hipLaunchKernel(ns_kernel_ptr(k), dim3(grid), dim3(block), args, 0, stream));
-    return MCALF_OK;
-}
-
-// logL of the `n` trial rows at Y into LY, exactly what mcalf_loglike_cube_batch_device(Y) writes.
-int trial_logl(mcalf_ctx* ctx, const double* Y, const double* LY, int64_t n, hipStream_t stream) {
-    LaunchReq q(kModeLogL, Y, n, stream);
-    q.d_out = const_cast<double*>(LY); q.from_cube = true;
-    return launch(ctx, q);
-}
+// What a failed launch of a kernel of ns_kernels.hip is reported as.
+constexpr char kNsLaunch[] = "hipLaunchKernel(ns_kernel_ptr(k), dim3(grid), dim3(block), args, 0, stream)";
 
 // The lock steps of a call that packs its trial rows (mcalf_set_slice_compact; host entry only).  Live rows only ever finish, so
 // the count of rows that proposed in step it - 1 bounds the count of step it: the launch of step it is sized by it, and the host
@@ -66,10 +56,14 @@ int compact_steps(mcalf_ctx* ctx, NsArgs& a, const mcalf_slice_opts& o, hipStrea
     int64_t n = a.nrows;                                // count(0): every row may propose in step 1
     for (int it = 1; it <= o.max_steps && o.nmoves > 0; ++it) {
         a.it = it; a.decide = *open_trial ? 1 : 0; a.propose = 1;
-        if ((rc = launch_ns(ctx, kNsStep, a, stream, (unsigned)a.nrows)) || (rc = launch_ns(ctx, kNsPack, a, stream, 1, kNsPackBlock))) return rc;
+        if ((rc = launch_block(ctx, ns_kernel_ptr(kNsStep), a, dim3((unsigned)a.nrows), dim3(kNsWave), stream, kNsLaunch)) ||
+            (rc = launch_block(ctx, ns_kernel_ptr(kNsPack), a, dim3(1), dim3(kNsPackBlock), stream, kNsLaunch)))
+            return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ns_live, a.live, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_ns, stream));
-        if ((rc = launch_ns(ctx, kNsGather, a, stream, (unsigned)n)) || (rc = trial_logl(ctx, a.Yc, a.LY, n, stream))) return rc;
+        if ((rc = launch_block(ctx, ns_kernel_ptr(kNsGather), a, dim3((unsigned)n), dim3(kNsWave), stream, kNsLaunch)) ||
+            (rc = cube_logl(ctx, a.Yc, a.LY, n, stream)))
+            return rc;
         *open_trial = true;
         st.steps += 1; st.rows_launched += n;
         HIP_TRY(ctx, hipEventSynchronize(ctx->ev_ns));
@@ -105,8 +99,10 @@ int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opt
     a.Y = ctx->nb[mcalf_ctx::kNbY]; a.LY = ctx->nb[mcalf_ctx::kNbLY]; a.brk = ctx->nb[mcalf_ctx::kNbBrk]; a.dir = ctx->ns_dir; a.live = ctx->d_ns_live;
     a.stamp = ctx->ns_pack;
     a.seed = o.seed; a.nrows = (int)batch; a.ndim = ctx->ndim; a.ndirs = o.ndirs; a.nmoves = o.nmoves;
-    const unsigned rows = (unsigned)batch;
-    if ((rc = launch_ns(ctx, kNsStart, a, stream, rows)) || (rc = trial_logl(ctx, a.Y, a.LY, batch, stream)) || (rc = launch_ns(ctx, kNsStarted, a, stream, rows))) return rc;
+    const dim3 rows((unsigned)batch), wave(kNsWave);
+    if ((rc = launch_block(ctx, ns_kernel_ptr(kNsStart), a, rows, wave, stream, kNsLaunch)) || (rc = cube_logl(ctx, a.Y, a.LY, batch, stream)) ||
+        (rc = launch_block(ctx, ns_kernel_ptr(kNsStarted), a, rows, wave, stream, kNsLaunch)))
+        return rc;
     bool open_trial = false;                            // the last trial has been evaluated and not yet decided on
     if (compact) {                                      // (from here on LY holds the logL of the packed rows, by slot)
         a.slot = ctx->ns_pack + nb; a.idx = ctx->ns_pack + 2 * nb; a.Yc = ctx->nb[mcalf_ctx::kNbYc];
@@ -115,9 +111,9 @@ int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opt
         for (int it = 1; it <= o.max_steps && o.nmoves > 0; ++it) {
             if (poll) HIP_TRY(ctx, hipMemsetAsync(a.live, 0, sizeof(unsigned int), stream));
             a.it = it; a.decide = open_trial ? 1 : 0; a.propose = 1;
-            if ((rc = launch_ns(ctx, kNsStep, a, stream, rows))) return rc;
+            if ((rc = launch_block(ctx, ns_kernel_ptr(kNsStep), a, rows, wave, stream, kNsLaunch))) return rc;
             if (poll) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_ns_live, a.live, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-            if ((rc = trial_logl(ctx, a.Y, a.LY, batch, stream))) return rc;
+            if ((rc = cube_logl(ctx, a.Y, a.LY, batch, stream))) return rc;
             open_trial = true;
             st.steps += 1; st.rows_launched += batch;
             if (poll) {
@@ -130,31 +126,30 @@ int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opt
     }
     if (open_trial) {
         a.it = o.max_steps + 1; a.decide = 1; a.propose = 0;
-        if ((rc = launch_ns(ctx, kNsStep, a, stream, rows))) return rc;
+        if ((rc = launch_block(ctx, ns_kernel_ptr(kNsStep), a, rows, wave, stream, kNsLaunch))) return rc;
     }
-    if (r.theta) {                                      // the transformed rows of the points, as the cube launch forms them
-        const double *lo = ctx->d_prior, *hi = ctx->d_prior + ndim, *cube = r.U;
-        long total = (long)(nb * ndim);
-        int nd = ctx->ndim, slot = ctx->startind, as_int = ctx->prior_int;
-        double* theta = r.theta;
-        void* kargs[] = {(void*)&lo, (void*)&hi, (void*)&cube, (void*)&total, (void*)&nd, (void*)&slot, (void*)&as_int, (void*)&theta};
-        HIP_TRY(ctx, hipLaunchKernel(scale_cube_kernel_ptr(), dim3((unsigned)((total + 255) / 256)), dim3(256), kargs, 0, stream));
-    }
+    if (r.theta) return cube_to_theta(ctx, r.U, r.theta, batch, stream);      // the transformed rows of the points
     return MCALF_OK;
 }
 
-struct NsShard { NsRows r; const mcalf_slice_opts* o; int64_t ndim; };
+// The host entry's device driver (host_staged.cpp: run_staged); columns in the order of NsCol.
+enum NsCol { kColU0, kColLmin, kColD, kColSid, kColU, kColTheta, kColL, kColStatus, kColNevals, kColMoves, kNsCols };
+
+int ns_body(mcalf_ctx* ctx, void** dev, int64_t rows, hipStream_t stream, void* arg) {
+    const NsRows d = {(const double*)dev[kColU0], (const double*)dev[kColLmin], (const double*)dev[kColD], (const uint64_t*)dev[kColSid],
+                      (double*)dev[kColU], (double*)dev[kColTheta], (double*)dev[kColL], (int32_t*)dev[kColStatus], (int32_t*)dev[kColNevals],
+                      (int32_t*)dev[kColMoves]};
+    return run_ns(ctx, d, rows, *static_cast<const mcalf_slice_opts*>(arg), stream, true);
+}
 
 int ns_host(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o) {
-    if (is_multi(ctx)) {                                  // contiguous row blocks, one per device, straight into the caller's arrays
-        NsShard c = {r, &o, ctx->ndim};
-        const int rc = multi_run(ctx, batch, [](void* sub, int64_t lo, int64_t hi, void* arg) {
-            const NsShard* s = static_cast<const NsShard*>(arg);
-            const size_t o0 = (size_t)lo * s->ndim;
-            const NsRows part = {s->r.U0 + o0, s->r.Lmin + lo, s->r.D, s->r.sid + lo, s->r.U + o0, s->r.theta ? s->r.theta + o0 : nullptr,
-                                 s->r.logL + lo, s->r.status + lo, s->r.nevals + lo, s->r.moves + lo};
-            return ns_host(static_cast<mcalf_ctx*>(sub), part, hi - lo, *s->o);
-        }, &c);
+    const size_t d = sizeof(double), i = sizeof(int32_t), ndim = (size_t)ctx->ndim;
+    StagePlan plan = {{stage_in(r.U0, d, ndim), stage_in(r.Lmin, d, 1), stage_in(r.D, d, (size_t)o.ndirs * ndim, false), stage_in(r.sid, sizeof(uint64_t), 1),
+                       stage_out(r.U, d, ndim), stage_out(r.theta, d, ndim), stage_out(r.logL, d, 1), stage_out(r.status, i, 1),
+                       stage_out(r.nevals, i, 1), stage_out(r.moves, i, 1)},
+                      kNsCols, batch, kStageCutRows, kColU0, kColU, ns_body, const_cast<mcalf_slice_opts*>(&o)};
+    const int rc = run_staged(ctx, plan);
+    if (is_multi(ctx)) {
         mcalf_slice_stats_t& st = ctx->ns_stats;          // the sum over the entries the call was cut over; the longest loop
         st = mcalf_slice_stats_t();
         st.compact = ctx->ns_compact;
@@ -163,33 +158,8 @@ int ns_host(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_op
             st.batch += e.batch; st.rows_launched += e.rows_launched; st.trials += e.trials;
             st.steps = std::max(st.steps, e.steps);
         }
-        return rc;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    begin_call(ctx, MCALF_PATH_HOST_STAGED, is_pinned_host(r.U0), is_pinned_host(r.U));
-    const size_t nb = (size_t)batch, n = nb * ctx->ndim, nd = (size_t)o.ndirs * ctx->ndim;
-    DevBuf<double>* b = ctx->nb;
-    int rc;
-    if ((rc = grow(ctx, b[mcalf_ctx::kNbU0], n)) || (rc = grow(ctx, b[mcalf_ctx::kNbU], n)) || (rc = grow(ctx, b[mcalf_ctx::kNbLmin], nb)) ||
-        (rc = grow(ctx, b[mcalf_ctx::kNbD], nd)) || (rc = grow(ctx, b[mcalf_ctx::kNbL], nb)) || (r.theta && (rc = grow(ctx, b[mcalf_ctx::kNbTheta], n))) ||
-        (rc = grow(ctx, ctx->ns_sid, nb)) || (rc = grow(ctx, ctx->ns_hst, 3 * nb)))
-        return rc;
-    const NsRows d = {b[mcalf_ctx::kNbU0], b[mcalf_ctx::kNbLmin], b[mcalf_ctx::kNbD], ctx->ns_sid, b[mcalf_ctx::kNbU],
-                      r.theta ? b[mcalf_ctx::kNbTheta].p : nullptr, b[mcalf_ctx::kNbL], ctx->ns_hst, ctx->ns_hst + nb, ctx->ns_hst + 2 * nb};
-    const hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kNbU0], r.U0, n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kNbLmin], r.Lmin, nb * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(b[mcalf_ctx::kNbD], r.D, nd * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ns_sid, r.sid, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if ((rc = run_ns(ctx, d, batch, o, st, true))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(r.U, d.U, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (r.theta) HIP_TRY(ctx, hipMemcpyAsync(r.theta, d.theta, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.logL, d.logL, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.status, d.status, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.nevals, d.nevals, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r.moves, d.moves, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return MCALF_OK;
+    return rc;
 }
 
 }  // namespace

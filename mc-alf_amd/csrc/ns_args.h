@@ -17,10 +17,6 @@ constexpr int kNsPackInts = 3;           // per-row integers of the packing: [0]
 // Status of a row.  0 while it is live (and at the end: max_steps reached).
 enum { kNsLive = 0, kNsDone = 1, kNsBadStart = -1 };
 
-// Philox4x64-10 (Salmon et al. 2011), the constants numpy's Philox bit generator uses.
-constexpr uint64_t kPhiloxM0 = 0xD2E7470EE14C6C93ull, kPhiloxM1 = 0xCA5A826395121157ull;
-constexpr uint64_t kPhiloxW0 = 0x9E3779B97F4A7C15ull, kPhiloxW1 = 0xBB67AE8584CAA73Bull;
-
 // One call of the replacement primitive (all `nrows` rows of it: the logL launch between two kernels cuts its own blocks).
 struct NsArgs {
     const double* U0;         // the caller's starts [nrows, ndim] (read by the start kernels only)

@@ -21,50 +21,9 @@
 
 #pragma clang fp contract(off)
 
+#include "wave_row.h"
+
 using namespace mcalf;
-
-namespace {
-
-__device__ __forceinline__ double uniform(double v) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const double o = __shfl_xor(v, m, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const double o = __shfl_xor(v, m, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-// Philox4x64-10 with counter (c0, 0, c2, 0) and key (k0, 0): words 0 and 1 of the block (2 and 3 are reserved).
-__device__ __forceinline__ void philox_words(uint64_t c0, uint64_t c2, uint64_t k0, uint64_t& w0, uint64_t& w1) {
-    uint64_t c1 = 0, c3 = 0, k1 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t hi0 = __umul64hi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
-        const uint64_t hi1 = __umul64hi(kPhiloxM1, c2), lo1 = kPhiloxM1 * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += kPhiloxW0; k1 += kPhiloxW1;
-    }
-    w0 = c0; w1 = c1;
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(kNsWave) void mcalf_slice_start_kernel(const NsArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
@@ -91,7 +50,7 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_started_kernel(const NsAr
     int bad = 0;
     for (int k = lane; k < a.ndim; k += kNsWave) {
         const double v = a.U0[o + k];
-        bad |= (v >= 0.0 && v <= 1.0) ? 0 : 1;
+        bad |= outside_unit(v);
     }
     const double l = a.LY[row];
     const bool outside = __any(bad);
@@ -128,8 +87,9 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_step_kernel(const NsArgs 
         }
     }
     if (!a.propose) return;
-    uint64_t w0, w1;
-    philox_words((uint64_t)a.it, a.sid[row], a.seed, w0, w1);
+    uint64_t w[4];                                             // (key word 1 is 0; words 2 and 3 are reserved)
+    philox4x64_10((uint64_t)a.it, a.sid[row], a.seed, 0, w);
+    const uint64_t w0 = w[0], w1 = w[1];
     if (dir < 0) {                                             // a new direction: the chord of its line through the cube
         dir = (int)(w0 % (uint64_t)a.ndirs);
         const double* d = a.D + (size_t)dir * a.ndim;
