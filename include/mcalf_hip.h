@@ -90,7 +90,9 @@ extern "C" {
                                     mcalf_set_slice_compact, mcalf_slice_last_stats: the host entry of the replacement step
                                     packs the rows that proposed a trial, and what a slice call launched;
                                     mcalf_ensemble_batch[_device], the ensemble MCMC sampler: stretch and DE moves of a walker
-                                    set in the unit cube, the chain kept on the device) */
+                                    set in the unit cube, the chain kept on the device;
+                                    mcalf_tempered_batch[_device], parallel tempering of that sampler: a ladder of temperatures
+                                    moved in the same launches, swaps between neighbours) */
 
 enum {
     MCALF_OK = 0,
@@ -617,6 +619,66 @@ int mcalf_ensemble_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, con
 int mcalf_ensemble_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const mcalf_ens_opts* opts, double* dU,
                                 double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept, double* dCU, double* dCL,
                                 void* stream);
+
+/* Parallel tempering of the ensemble sampler: T = ntemps temperatures (1 <= T <= MCALF_PT_MAX_TEMPS) of n = nwalkers walkers
+ * each, temperature t sampling logL^beta[t].  `beta` is a HOST array of T doubles in both entries, read during the call as opts
+ * is: every beta finite and >= 0, strictly decreasing in t (beta[0] = 1 is the posterior, beta[T - 1] = 0 the prior).  The state
+ * is U [T][n][ndim] and logL [T][n]; row t n + w of every array is walker w of temperature t, and the logL stored is always the
+ * UNTEMPERED value of mcalf_loglike_cube_batch.  Every temperature is cut into the halves [0, m) and [m, n), m = n / 2.
+ *   start    logL(U0) by one cube launch over all T n rows.  A position (t, w) whose start has an entry outside [0, 1] or a NaN
+ *            has status -1: it never moves and never swaps (others may draw it as a partner, of a move or of a swap).
+ *   half-step  the ensemble sampler's, for every temperature at once: the partners of walker (t, w) come from the other half
+ *            of temperature t; its words are the block numpy's Philox(counter=[s, 0, t n + w, 0], key=[seed, 1]) returns first,
+ *            s = 2 (first_iter + i) + h (at T = 1 the ensemble sampler's words); xi, zeta and the proposals of both moves are
+ *            as above.  y not inside: rejected, as above.  Otherwise d = logL(y) - logL(x);  q = hastings + beta[t] d with
+ *            hastings = (ndim - 1) ln z for the stretch move, and q = beta[t] d for the DE move;  accepted iff ln zeta < q
+ *            (any NaN: false -- a trial of -inf is rejected at every beta, beta = 0 included, where 0 (-inf) is NaN).
+ *            beta[t] d is one rounded product; at beta = 1 it is d.  One propose kernel over T m blocks, one cube logL launch
+ *            over the T m trial rows, one decide kernel.
+ *   swaps    g = first_iter + i is the global iteration.  After the second half-step of every iteration with
+ *            (g + 1) mod swap_every == 0 (swap_every 0: never) and before the chain slot is filled, swap round
+ *            r = (g + 1) / swap_every - 1 is made: the pairs of temperatures (t, t + 1) for every t = r mod 2, r mod 2 + 2, ...
+ *            with t + 1 < T (disjoint).  Pair t has the shift c = w0 mod n, w0 from the block numpy's
+ *            Philox(counter=[r, 1, t, 0], key=[seed, 2]) returns first (the function at counter (r + 1, 1, t, 0)); position
+ *            (t, w) meets position (t + 1, j), j = (w + c) mod n -- a bijection, so every row is in at most one exchange of the
+ *            round.  zeta = ((w2 >> 11) + 1) 2^-53 from the block of Philox(counter=[r, 0, t n + w, 0], key=[seed, 2]);
+ *            q = (beta[t] - beta[t + 1]) (logL[t + 1][j] - logL[t][w])  (a difference, a difference, a product);
+ *            the two are exchanged iff both positions have status 0 and ln zeta < q (any NaN: false): the two U rows in all
+ *            ndim coordinates and the two logL values change places, nswap[t][w] + 1.  status, naccept and nswap belong to
+ *            positions, not to states.  nswap [T - 1][n] counts the accepted swaps of position (t, w) with temperature t + 1
+ *            (T = 1: not touched, may be NULL).
+ *   chain    after every iteration i (call-local) with (i + 1) mod thin == 0 the state after that iteration's swaps goes into
+ *            slot (i + 1) / thin - 1 of CL [nkeep][T][n] (all temperatures: the evidence needs them) and of
+ *            CU [nkeep][chain_temps][n][ndim] (the first chain_temps temperatures, 0 <= chain_temps <= T).
+ * The arithmetic rules, ln and the 4 GiB cap on the chain are the ensemble sampler's.  A position's results depend on (U0, beta,
+ * opts) alone; taking the last U as U0 with first_iter advanced by nsteps is, bit for bit, the longer call (the swap rounds are
+ * keyed to g).  With ntemps = 1 and beta = {1} the results are mcalf_ensemble_batch's bit for bit. */
+enum { MCALF_PT_MAX_TEMPS = 64 };
+typedef struct {
+    int32_t nsteps;          /* iterations, >= 0 (0: the checked start and its logL) */
+    int32_t thin;            /* every thin-th iteration goes into the chain, >= 1 */
+    int32_t move;            /* MCALF_ENS_STRETCH or MCALF_ENS_DE */
+    int32_t ntemps;          /* T, 1 .. MCALF_PT_MAX_TEMPS */
+    int32_t swap_every;      /* a swap round after every swap_every-th global iteration, >= 0 (0: never) */
+    int32_t chain_temps;     /* temperatures whose rows CU keeps, 0 .. T */
+    double scale;            /* a > 1 of the stretch move, g > 0 of the DE move; finite */
+    uint64_t seed;           /* the Philox key word 0 */
+    uint64_t first_iter;     /* the global iteration number of the call's first iteration (continuation) */
+} mcalf_pt_opts;             /* 48 bytes */
+/* Host pointers, synchronous: U, theta (T n x ndim; theta NULL: not wanted), logL, status, naccept (T n each), nswap
+ * ((T - 1) n) and the chain CU, CL (each NULL: not wanted) are outputs; U0 and U must not overlap.  A multi-device context runs
+ * the whole call on its first device entry: bit for bit a single-device context's result.  All argument checks come before any
+ * device work and name the argument: mcalf_ensemble_batch's, and beta NULL; ntemps outside [1, 64]; a beta that is not finite, is
+ * negative or is not below its predecessor; swap_every < 0; chain_temps outside [0, T]; nswap NULL with T > 1; ntemps x nwalkers
+ * above 0x7fff0000 rows (MCALF_ERR_RANGE).  nwalkers == 0 does nothing. */
+int mcalf_tempered_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, const double* beta, const mcalf_pt_opts* opts, double* U,
+                         double* theta, double* logL, int32_t* status, int32_t* naccept, int32_t* nswap, double* CU, double* CL);
+/* Same, device pointers (beta and opts are host arrays, read during the call: beta travels in the kernels' argument block), on
+ * the caller's stream (single-device contexts).  It never synchronises; the bits are the host entry's.  After one call of the
+ * same or a larger size it allocates nothing. */
+int mcalf_tempered_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const double* beta, const mcalf_pt_opts* opts,
+                                double* dU, double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept, int32_t* dnswap,
+                                double* dCU, double* dCL, void* stream);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

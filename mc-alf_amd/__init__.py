@@ -12,6 +12,7 @@ from . import dist  # noqa: F401
 from . import ensemble  # noqa: F401
 from . import nested  # noqa: F401
 from . import routines  # noqa: F401
+from . import tempering  # noqa: F401
 from . import workloads  # noqa: F401
 from .routines import hires_fitter  # noqa: F401
 from .routines.hires_fitter import als_fitter  # noqa: F401

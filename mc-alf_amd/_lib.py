@@ -160,6 +160,23 @@ class mcalf_ens_opts(C.Structure):
     ]
 
 
+class mcalf_pt_opts(C.Structure):
+    _fields_ = [
+        ("nsteps", C.c_int32),
+        ("thin", C.c_int32),
+        ("move", C.c_int32),
+        ("ntemps", C.c_int32),
+        ("swap_every", C.c_int32),
+        ("chain_temps", C.c_int32),
+        ("scale", C.c_double),
+        ("seed", C.c_uint64),
+        ("first_iter", C.c_uint64),
+    ]
+
+
+# the largest ladder of mcalf_tempered_batch
+MCALF_PT_MAX_TEMPS = 64
+
 # the moves of mcalf_ensemble_batch
 MCALF_ENS_STRETCH, MCALF_ENS_DE = 0, 1
 
@@ -219,6 +236,10 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_ensemble_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_tempered_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcalf_tempered_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -3,8 +3,8 @@
 The library is twenty-three translation units: the seven device files of DEVICE_OBJECTS -- kernels.hip (the likelihood's
 kernels), grad_kernels.hip (the analytic gradient's and the Jacobian products'), eqw_kernels.hip (the equivalent widths'),
 band_kernels.hip (the posterior bands'), fit_kernels.hip (the fit's and the Fisher product's), ns_kernels.hip (nested sampling's
-replacement step) and ens_kernels.hip (the ensemble sampler's moves) -- and the host side of the C ABI, HOST_SOURCES, compiled
-as plain C++ against the HIP runtime API.  Objects are kept under csrc/obj/ so that an edit of a host file does not recompile
+replacement step) and ens_kernels.hip (the ensemble sampler's moves and its temperature swaps) -- and the host side of the C
+ABI, HOST_SOURCES, compiled as plain C++ against the HIP runtime API.  Objects are kept under csrc/obj/ so that an edit of a host file does not recompile
 the kernels (22 s), and an edit of one device file does not recompile the others."""
 from __future__ import annotations
 

@@ -317,8 +317,8 @@ struct mcalf_ctx {
     hipEvent_t ev_ns = nullptr;
     int ns_compact = 0;                     // MCALF_NS_COMPACT / mcalf_set_slice_compact
     mcalf_slice_stats_t ns_stats = {};
-    // The ensemble sampler (host_ens.cpp), grown on demand.  The trial rows [m][ndim] of the moving half, their logL [m], the
-    // Hastings term and ln zeta [2][m] and the inside flags [m] of one half-step.  The chain is NOT among them: the host entry
+    // The ensemble sampler (host_ens.cpp), grown on demand.  The trial rows [T m][ndim] of the moving halves of its T temperatures
+    // (mcalf_ensemble_batch: one), their logL [T m], the Hastings term and ln zeta [2][T m] and the inside flags [T m] of one half-step.  The chain is NOT among them: the host entry
     // releases it before it returns, the device entry is handed the caller's.
     enum { kEnY, kEnLY, kEnAux, kEnCount };
     DevBuf<double> enb[kEnCount];

@@ -53,9 +53,9 @@ __device__ __forceinline__ int outside_unit(double v) { return (v >= 0.0 && v <=
 constexpr uint64_t kPhiloxM0 = 0xD2E7470EE14C6C93ull, kPhiloxM1 = 0xCA5A826395121157ull;
 constexpr uint64_t kPhiloxW0 = 0x9E3779B97F4A7C15ull, kPhiloxW1 = 0xBB67AE8584CAA73Bull;
 
-// The block of counter (c0, 0, c2, 0) under key (k0, k1): its four words.
-__device__ __forceinline__ void philox4x64_10(uint64_t c0, uint64_t c2, uint64_t k0, uint64_t k1, uint64_t (&w)[4]) {
-    uint64_t c1 = 0, c3 = 0;
+// The block of counter (c0, c1, c2, 0) under key (k0, k1): its four words.
+__device__ __forceinline__ void philox4x64_10(uint64_t c0, uint64_t c1, uint64_t c2, uint64_t k0, uint64_t k1, uint64_t (&w)[4]) {
+    uint64_t c3 = 0;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint64_t hi0 = __umul64hi(kPhiloxM0, c0), lo0 = kPhiloxM0 * c0;
@@ -65,6 +65,10 @@ __device__ __forceinline__ void philox4x64_10(uint64_t c0, uint64_t c2, uint64_t
         k0 += kPhiloxW0; k1 += kPhiloxW1;
     }
     w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// The block of counter (c0, 0, c2, 0).
+__device__ __forceinline__ void philox4x64_10(uint64_t c0, uint64_t c2, uint64_t k0, uint64_t k1, uint64_t (&w)[4]) {
+    philox4x64_10(c0, 0, c2, k0, k1, w);
 }
 
 }  // namespace mcalf

@@ -641,6 +641,66 @@ class als_fitter:
         return ensemble.ensemble_sample(lambda U: self.loglike_cube_batch(U), advance, self.ndim, nwalkers, nsteps, burn=burn, thin=thin,
                                         start=start, ball=ball, seed=seed)
 
+    def tempered_batch(self, U0, betas, nsteps, thin=1, swap_every=1, move="stretch", scale=None, seed=0, first_iter=0, chain=True, chain_temps=1):
+        """(U, theta, logL, status, naccept, nswap, chainU, chainL): `nsteps` iterations of the ensemble sampler of
+        `ensemble_batch` at T = len(betas) temperatures at once, with swaps between neighbouring temperatures
+        (`mcalf_tempered_batch`; HIP kernels).  U0 [T, nwalkers, ndim] holds the starts of every rung (unit cube; nwalkers even,
+        >= 4); rung t samples logL^betas[t] (betas finite, >= 0, strictly decreasing; 1 <= T <= 64).  A half-step moves one half
+        of every rung, T x nwalkers / 2 trial rows through one likelihood launch; after every global iteration g with
+        (g + 1) % swap_every == 0 (0: never) every other pair of neighbouring rungs, alternating from round to round, exchanges
+        walkers along a random shift, a swap costing no likelihood evaluation.
+
+        U, theta [T, nwalkers, ndim], logL, status, naccept [T, nwalkers]: as `ensemble_batch`'s, per position; logL is always
+        the untempered `loglike_cube_batch` value.  nswap [T - 1, nwalkers]: accepted swaps of position (t, w) with rung t + 1.
+        chainL [nsteps // thin, T, nwalkers] keeps logL of every rung (the evidence needs them), chainU
+        [nsteps // thin, chain_temps, nwalkers, ndim] the rows of the first `chain_temps` rungs (`chain=False`: None, None).
+        The random words are Philox4x64-10 of (half-step or swap round, position, seed): calling again with the returned U and
+        `first_iter` advanced by `nsteps` is, bit for bit, the longer call, and one rung at beta = 1 is `ensemble_batch`."""
+        U0 = np.ascontiguousarray(U0, dtype=float)
+        betas = np.ascontiguousarray(betas, dtype=float).reshape(-1)
+        T = betas.size
+        if U0.ndim != 3 or U0.shape[0] != T or U0.shape[2] != self.ndim:
+            raise ValueError(f"U0 must be [len(betas) = {T}, nwalkers, ndim = {self.ndim}], got {U0.shape}")
+        n = U0.shape[1]
+        moves = {"stretch": _lib.MCALF_ENS_STRETCH, "de": _lib.MCALF_ENS_DE}
+        if move not in moves:
+            raise ValueError(f"move must be 'stretch' or 'de', got {move!r}")
+        if scale is None:
+            scale = 2.0 if move == "stretch" else 2.38 / np.sqrt(2.0 * self.ndim)
+        nsteps, thin, chain_temps = int(nsteps), int(thin), int(chain_temps)
+        self._ensure_prior()
+        opts = _lib.mcalf_pt_opts(nsteps, thin, moves[move], T, int(swap_every), chain_temps, float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  int(first_iter) & 0xFFFFFFFFFFFFFFFF)
+        U, theta = np.empty_like(U0), np.empty_like(U0)
+        logL = np.empty((T, n))
+        status, naccept = (np.empty((T, n), dtype=np.int32) for _ in range(2))
+        nswap = np.zeros((max(T - 1, 0), n), dtype=np.int32)
+        nkeep = nsteps // thin if chain and nsteps >= 0 and thin >= 1 else 0
+        CU, CL = (np.empty((nkeep, min(max(chain_temps, 0), T), n, self.ndim)), np.empty((nkeep, T, n))) if chain else (None, None)
+        _lib.check(self._lib.mcalf_tempered_batch(self._ctx, self._ptr(U0), n, self._ptr(betas), C.addressof(opts), self._ptr(U), self._ptr(theta),
+                                                  self._ptr(logL), status.ctypes.data, naccept.ctypes.data, nswap.ctypes.data,
+                                                  self._ptr(CU) if chain else None, self._ptr(CL) if chain else None), self._ctx)
+        return U, theta, logL, status, naccept, nswap, CU, CL
+
+    def tempered_sample(self, nwalkers, nsteps, ntemps=8, betas=None, burn=0, thin=1, swap_every=1, start=None, ball=None, seed=0, move="stretch",
+                        scale=None):
+        """Parallel tempering of this problem's posterior with the device's own two entries: `tempered_batch` for the burn-in
+        and for the kept run (two calls, whatever their length) and `loglike_cube_batch` for the transformed rows of the cold
+        rung (`tempering.tempered_sample` keeps the books).  `betas` (None: `tempering.default_ladder(ntemps, 1e-4)`, which
+        ends at the prior) is the ladder; every rung holds `nwalkers` walkers, started uniformly in the cube or in a ball of
+        half-width `ball` around the cube point `start`.  Returns a `tempering.TemperedResult`: logL of every rung, the
+        acceptance and swap fractions per rung, `cold()` -- the beta[0] rung as an `ensemble.EnsembleResult` -- and the
+        evidence by `logZ_stepping_stone()` and `logZ_ti()`."""
+        from .. import tempering
+        betas = tempering.default_ladder(ntemps, 1e-4) if betas is None else betas
+
+        def advance(U0, nsteps, thin=1, swap_every=1, seed=0, first_iter=0, chain=True, chain_temps=1):
+            return self.tempered_batch(U0, betas, nsteps, thin=thin, swap_every=swap_every, move=move, scale=scale, seed=seed, first_iter=first_iter,
+                                       chain=chain, chain_temps=chain_temps)
+
+        return tempering.tempered_sample(lambda U: self.loglike_cube_batch(U), advance, self.ndim, nwalkers, nsteps, betas, burn=burn, thin=thin,
+                                         swap_every=swap_every, start=start, ball=ball, seed=seed)
+
     def loglike_hvp_batch(self, P, V, out=None):
         """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's
         `conv_mode` applied to one tangent per row ([batch, ndim] -> [batch, ndim]; HIP kernels, H is never formed).  It is
