@@ -773,6 +773,50 @@ int mcalf_loglike_cube_batch(mcalf_ctx* ctx, const double* cube, int64_t batch, 
 int mcalf_loglike_cube_batch_device(mcalf_ctx* ctx, const double* dcube, int64_t batch, double* dtheta,
                                     double* dlogL, void* stream);
 
+/* Gaussian priors (the reference's Gpriors keyword: lnprior, hires_fitter.py:218-234, and __call__, :509-518); added within
+ * ABI 9.  The prior of a context is its box times one Gaussian factor per parameter that carries one, NOT renormalised for the
+ * truncation by the box (the reference's convention, :230).  For a row theta, the box lo / hi and mu[k], sigma[k]:
+ *   lnprior(theta) = -inf                                                       if any theta_k is NaN or outside [lo_k, hi_k]
+ *                  = sum over k with sigma[k] > 0 of  -0.5 (((theta_k - mu[k]) / sigma[k])^2 + c_k),  c_k = ln(2 pi sigma[k]^2)
+ *                    otherwise; with no Gaussian coordinate the sum is an exact 0.
+ * The arithmetic is a fixed sequence of separately rounded IEEE operations (no FMA), so that numpy restates it bit for bit
+ * (tests/prior_reference.py):
+ *   c_k     computed ONCE by std::log on the host when the prior is set, and stored: mcalf_get_gauss_prior returns the bits
+ *   theta_k the row's entry; for a unit-cube row u:  p = u_k (hi_k - lo_k);  theta_k = p + lo_k   (the arithmetic of
+ *           mcalf_scale_cube_batch, so theta has the bits mcalf_loglike_cube_batch returns; the ncomp slot never carries a
+ *           Gaussian, so its truncation does not enter).  A cube entry outside [0, 1] or NaN: -inf
+ *   term    d = (theta_k - mu_k) / sigma_k;  dd = d d;  s = dd + c_k;  term = -0.5 s
+ *   row     ONE wave64 owns a row, lane l owns coordinates l, l + 64, ...: it adds its terms in index order onto +0.0
+ *           (coordinates with sigma[k] == 0 are skipped, not added as zeros); the 64 lane sums are folded by the xor-butterfly
+ *           v <- v + v[lane ^ m], m = 32, 16, ..., 1.
+ *
+ * mcalf_set_gauss_prior: mu, sigma [ndim] host arrays (copied); needs mcalf_set_prior first.  sigma[k] == 0: no Gaussian on k.
+ * Refused with MCALF_ERR_INVALID, naming the argument and the index, before any device work: sigma[k] negative, NaN or
+ * infinite; a non-finite mu[k] where sigma[k] > 0; sigma[k] > 0 on the ncomp slot (the box truncates that slot to an integer: a
+ * density on it has no defined mass).  NULL, NULL clears the prior.  A later mcalf_set_prior with another box keeps the
+ * Gaussian.  On a multi-device context every device entry receives it.
+ * mcalf_get_gauss_prior: what the kernels use -- mu, sigma, c [ndim] (each may be NULL; zeros when none is set) and the number
+ * of Gaussian coordinates (0 when none is set).
+ * mcalf_lnprior_batch: rows [batch][ndim] -> lnprior [batch]; from_cube 1: unit-cube rows, 0: parameter rows.  With no Gaussian
+ * set: 0 / -inf by the box test alone.  A multi-device context cuts the rows over its devices.  batch == 0 does nothing.
+ * mcalf_lnprior_batch_device: the same over device pointers on `stream`; never synchronises, never allocates; refuses a
+ * multi-device context.
+ *
+ * What honours it.  mcalf_slice_replace_batch[_device]: the constrained quantity is logL + lnprior (one rounded add), for the
+ * start's test against Lmin, for every trial, and in the returned logL, which is then
+ * mcalf_loglike_cube_batch(U) + mcalf_lnprior_batch(U, from_cube = 1) bit for bit -- nested sampling of L g under the box
+ * measure.  mcalf_ensemble_batch / mcalf_tempered_batch[_device]: logL, CL and the temperature stay the likelihood's; the accept
+ * rule of a half-step is  q = (h + beta (ly - lx)) + (py - px)  for the stretch move (h its Hastings term) and
+ * q = beta (ly - lx) + (py - px)  for the DE move, py / px lnprior of the trial and of the walker; a proposal outside the cube
+ * never has its prior read; a swap's rule is unchanged (the prior cancels between rungs), and the rung at beta = 0 samples the
+ * Gaussian factors over the cube.  With no Gaussian set all of them run the code path, and return the bits, they did before.
+ * mcalf_maximize_batch does NOT: it maximises logL alone (a MAP fit needs a diagonal term in its CG operator). */
+int mcalf_set_gauss_prior(mcalf_ctx* ctx, const double* mu, const double* sigma);
+int mcalf_get_gauss_prior(const mcalf_ctx* ctx, double* mu, double* sigma, double* c, int32_t* ngauss);
+int mcalf_lnprior_batch(mcalf_ctx* ctx, const double* rows, int64_t batch, int32_t from_cube, double* lnprior);
+int mcalf_lnprior_batch_device(mcalf_ctx* ctx, const double* drows, int64_t batch, int32_t from_cube, double* dlnprior,
+                               void* stream);
+
 /* Multi-GPU inside the library (the reference's only parallelism is data parallelism over live
  * points: PolyChord's MPI workers cli.py:110, jaxns' vmap cli.py:275-280).  One process per GPU, each with its own
  * context; the context owns an RCCL communicator (xGMI on one node).  Rank 0 obtains a 128-byte id with

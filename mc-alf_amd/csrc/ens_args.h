@@ -7,11 +7,13 @@
 #include <cstdint>
 
 #include "kernel_args.h"
+#include "prior_args.h"
 
 namespace mcalf {
 
 constexpr int kEnsWave = 64;             // threads per workgroup: ONE wave per walker, lane k owns coordinates k, k + 64, ...
-constexpr int kEnsAux = 2;               // per-moving-walker scalars in `aux`: [0][m] the Hastings term, [1][m] ln zeta
+constexpr int kEnsAux = 3;               // per-moving-walker scalars in `aux`: [0][m] the Hastings term, [1][m] ln zeta, [2][m] lnprior of
+                                         // an inside trial (written and read under a Gaussian prior only)
 constexpr uint64_t kEnsKey1 = 1;         // key word 1 of the ensemble's Philox streams (nested sampling's is 0)
 constexpr uint64_t kEnsKey2 = 2;         // key word 1 of the swap rounds' streams (mcalf_tempered_batch)
 constexpr int kEnsMaxTemps = 64;         // temperatures of one call at most: their beta travel in the argument block
@@ -55,11 +57,13 @@ struct EnsArgs {
     int ntemps, chain_temps;  // T; the temperatures whose rows go into CU (the first ones)
     int pair0;                // the swap round's first pair (r mod 2): its pairs are (pair0 + 2 p, pair0 + 2 p + 1)
     double beta[kEnsMaxTemps];   // the inverse temperatures, [0, T) used
+    PriorDev prior;           // prior.mu != NULL (a Gaussian prior is set): the accept rule gains lnprior(y) - lnprior(x), untempered
+    double* PR;               // lnprior of the walkers [T n] (a workspace of the call; NULL without a Gaussian prior)
 };
 
 // The kernels of ens_kernels.hip; all take (const EnsArgs a), kEnsWave threads.
 enum EnsKernel {
-    kEnsStart,        // grid T n: U = U0, naccept 0 (nswap 0), status -1 for a start outside the cube or with a NaN, else 0
+    kEnsStart,        // grid T n: U = U0, naccept 0 (nswap 0), status -1 for a start outside the cube or with a NaN, else 0; PR
     kEnsPropose,      // grid T m: the trial row of moving walker t n + half m + b, its Hastings term, ln zeta and inside flag
     kEnsDecide,       // grid T m: accept or reject it; with `keep`, the block then copies walkers b and m + b of its temperature into the chain slot
     kEnsSwap,         // grid (pairs of the round) n: one exchange between position (t, w) and its partner in temperature t + 1

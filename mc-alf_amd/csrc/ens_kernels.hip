@@ -17,12 +17,17 @@
 // Every product, quotient, sum and difference of the proposal, of ens_ln and of the accept rules is a separately rounded IEEE
 // operation: contraction to FMA is switched off for this whole file (as in ns_kernels.hip), so that numpy restates a run exactly
 // (tests/ens_reference.py, tests/pt_reference.py).  No atomics: a swap round's exchanges are disjoint pairs of rows.
+// Under a Gaussian prior (mcalf_set_gauss_prior; a.prior.mu != NULL) L, CL and the temperature stay the likelihood's; PR [T n]
+// holds lnprior of the walkers (row_lnprior of prior_device.h: the start kernel fills it, the propose kernel hands an inside
+// trial's value over through aux[2], a swap exchanges it with L), and the accept rule is q + (py - px).  Without one no kernel
+// reads or writes PR or aux[2].
 #include <hip/hip_runtime.h>
 
 #include "ens_args.h"
 
 #pragma clang fp contract(off)
 
+#include "prior_device.h"
 #include "wave_row.h"
 
 using namespace mcalf;
@@ -58,7 +63,9 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_start_kernel(const EnsArgs
         bad |= outside_unit(v);
     }
     const bool outside = __any(bad);
+    const double pr = a.prior.mu ? row_lnprior(a.prior, a.U0 + o, 1) : 0.0;
     if (lane != 0) return;
+    if (a.prior.mu) a.PR[w] = pr;
     a.status[w] = outside ? kEnsBadStart : kEnsOk;
     a.naccept[w] = 0;
     if (w < (a.ntemps - 1) * a.n) a.nswap[w] = 0;
@@ -105,7 +112,10 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_propose_kernel(const EnsAr
     const bool outside = __any(out);
     if (outside)                                               // the trial row is the walker's own point, as a finished slice row's
         for (int k = lane; k < a.ndim; k += kEnsWave) y[k] = x[k];
+    // lnprior of an inside trial, while the wave has y: every lane reads back the entries it wrote itself
+    const double py = a.prior.mu && !outside ? row_lnprior(a.prior, y, 1) : 0.0;
     if (lane != 0) return;
+    if (a.prior.mu && !outside) a.aux[2 * (size_t)a.ntemps * a.m + b] = py;
     a.aux[b] = hastings;
     a.aux[(size_t)a.ntemps * a.m + b] = ens_ln(zeta);
     a.inside[b] = outside ? 0 : 1;
@@ -120,11 +130,17 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_decide_kernel(const EnsArg
         const double* y = a.Y + (size_t)b * a.ndim;
         const double ly = a.LY[b], lx = a.L[w];
         const double d = a.beta[t] * (ly - lx);                // (beta 0 and a trial of -inf: NaN, rejected)
-        const double q = a.move == kEnsStretch ? a.aux[b] + d : d;
+        double q = a.move == kEnsStretch ? a.aux[b] + d : d;
+        double py = 0.0;
+        if (a.prior.mu) {                                      // the prior's ratio, untempered: (aux + beta d) + (py - px)
+            py = a.aux[2 * (size_t)a.ntemps * a.m + b];
+            q = q + (py - a.PR[w]);
+        }
         if (a.aux[(size_t)a.ntemps * a.m + b] < q) {           // (any NaN: false)
             for (int k = lane; k < a.ndim; k += kEnsWave) x[k] = y[k];
             if (lane == 0) {
                 a.L[w] = ly;
+                if (a.prior.mu) a.PR[w] = py;
                 a.naccept[w] += 1;
             }
         }
@@ -169,6 +185,11 @@ __global__ __launch_bounds__(kEnsWave) void mcalf_ens_swap_kernel(const EnsArgs 
     if (lane != 0) return;
     a.L[lo] = lh;
     a.L[hi] = ll;
+    if (a.prior.mu) {                                          // (the prior cancels in the rule above; the rows take theirs along)
+        const double pl = a.PR[lo];
+        a.PR[lo] = a.PR[hi];
+        a.PR[hi] = pl;
+    }
     a.nswap[lo] += 1;
 }
 

@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
 #pragma once
@@ -25,6 +25,7 @@
 #pragma GCC visibility pop
 #include "kernel_args.h"
 #include "grad_args.h"
+#include "prior_args.h"
 
 #define MCALF_STR_(x) #x
 #define MCALF_STR(x) MCALF_STR_(x)
@@ -203,6 +204,11 @@ struct mcalf_ctx {
     // prior box of mcalf_set_prior (device copy in d_prior: lo[ndim] then hi[ndim])
     bool prior_set = false;
     int prior_int = 0;
+    // Gaussian factors of mcalf_set_gauss_prior (host_prior.cpp), next to the box: mu[ndim], sigma[ndim], c[ndim] on the device and
+    // on the host, and the number of coordinates that carry one (0: none is set; a multi-device parent holds the count alone)
+    DevBuf<double> d_gauss;
+    std::vector<double> h_gauss;
+    int ngauss = 0;
     // Chunked issue: a batch is cut into row blocks that go to the caller's stream and to context-owned
     // auxiliary streams (fork / join through events), so that the set-up kernel and the first workgroups of
     // block k+1 run in the tail of block k.  chunks_req: 0 = automatic, n = exactly n blocks (1 = off).
@@ -323,6 +329,7 @@ struct mcalf_ctx {
     enum { kEnY, kEnLY, kEnAux, kEnCount };
     DevBuf<double> enb[kEnCount];
     DevBuf<int32_t> ens_inside;
+    DevBuf<double> ens_pr;                  // lnprior of the walkers [T n], grown by a call under a Gaussian prior only
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields are copies of sub-context 0's, for mcalf_info).
@@ -521,6 +528,14 @@ struct Product {
 };
 extern const Product kProdGrad, kProdJvp, kProdVjp, kProdHvp;
 int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStream_t stream);   // product `p` over device rows, on `stream`
+
+// ---- host_prior.cpp: the Gaussian prior -----------------------------------------------------------------------------------
+// The prior block of a (single-device) context whose box is set, for a kernel's arguments; mu is NULL when no Gaussian is set.
+inline PriorDev prior_dev(const mcalf_ctx* ctx) {
+    const double* g = ctx->ngauss > 0 ? ctx->d_gauss.p : nullptr;
+    const size_t n = (size_t)ctx->ndim;
+    return {ctx->d_prior, ctx->d_prior + n, g, g ? g + n : nullptr, g ? g + 2 * n : nullptr, ctx->ndim};
+}
 
 // ---- host_eqw.cpp: the equivalent-width entries -------------------------------------------------------------------------
 int eqw_prepare(mcalf_ctx* ctx, const double* wl);     // mcalf_create: dlam on the device

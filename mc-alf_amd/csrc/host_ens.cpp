@@ -93,7 +93,8 @@ int run_ens(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_pt_opts& o,
     const size_t T = (size_t)o.ntemps, nb = (size_t)n, m = nb / 2, ndim = (size_t)ctx->ndim, rows = T * nb, moving = T * m;
     int rc;
     if ((rc = grow(ctx, ctx->enb[mcalf_ctx::kEnY], moving * ndim)) || (rc = grow(ctx, ctx->enb[mcalf_ctx::kEnLY], moving)) ||
-        (rc = grow(ctx, ctx->enb[mcalf_ctx::kEnAux], moving * kEnsAux)) || (rc = grow(ctx, ctx->ens_inside, moving)))
+        (rc = grow(ctx, ctx->enb[mcalf_ctx::kEnAux], moving * kEnsAux)) || (rc = grow(ctx, ctx->ens_inside, moving)) ||
+        (ctx->ngauss > 0 && (rc = grow(ctx, ctx->ens_pr, rows))))
         return rc;
     EnsArgs a = {};
     a.U0 = r.U0; a.U = r.U; a.L = r.logL; a.status = r.status; a.naccept = r.naccept; a.nswap = r.nswap;
@@ -101,6 +102,8 @@ int run_ens(mcalf_ctx* ctx, const EnsRows& r, int64_t n, const mcalf_pt_opts& o,
     a.seed = o.seed; a.scale = o.scale; a.n = (int)n; a.m = (int)m; a.ndim = ctx->ndim; a.move = o.move;
     a.ntemps = o.ntemps; a.chain_temps = o.chain_temps;
     for (size_t t = 0; t < T; ++t) a.beta[t] = beta[t];
+    a.prior = prior_dev(ctx);
+    a.PR = a.prior.mu ? ctx->ens_pr.p : nullptr;
     const dim3 all((unsigned)rows), half((unsigned)moving), wave(kEnsWave);
     if ((rc = launch_block(ctx, ens_kernel_ptr(kEnsStart), a, all, wave, stream, kEnsLaunch)) || (rc = cube_logl(ctx, a.U, a.L, (int64_t)rows, stream))) return rc;
     double* const chainU = o.chain_temps > 0 ? r.CU : nullptr;

@@ -98,6 +98,7 @@ int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opt
     a.U0 = r.U0; a.Lmin = r.Lmin; a.D = r.D; a.sid = r.sid; a.U = r.U; a.L = r.logL; a.status = r.status; a.nevals = r.nevals; a.moves = r.moves;
     a.Y = ctx->nb[mcalf_ctx::kNbY]; a.LY = ctx->nb[mcalf_ctx::kNbLY]; a.brk = ctx->nb[mcalf_ctx::kNbBrk]; a.dir = ctx->ns_dir; a.live = ctx->d_ns_live;
     a.stamp = ctx->ns_pack;
+    a.prior = prior_dev(ctx);
     a.seed = o.seed; a.nrows = (int)batch; a.ndim = ctx->ndim; a.ndirs = o.ndirs; a.nmoves = o.nmoves;
     const dim3 rows((unsigned)batch), wave(kNsWave);
     if ((rc = launch_block(ctx, ns_kernel_ptr(kNsStart), a, rows, wave, stream, kNsLaunch)) || (rc = cube_logl(ctx, a.Y, a.LY, batch, stream)) ||

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "kernel_args.h"
+#include "prior_args.h"
 
 namespace mcalf {
 
@@ -37,6 +38,7 @@ struct NsArgs {
     int32_t* idx;             // [nrows] the packed rows of the step: idx[s] is the row of slot s, ascending
     double* Yc;               // the packed trial rows [nrows, ndim], what the logL launch evaluates when the rows are packed
     uint64_t seed;
+    PriorDev prior;           // prior.mu != NULL (a Gaussian prior is set): the constrained quantity is logL + lnprior
     int nrows, ndim, ndirs, nmoves;
     int it;                   // the step, 1 .. max_steps (+ 1: the last trial is decided, nothing is proposed)
     int decide, propose;
@@ -45,7 +47,7 @@ struct NsArgs {
 // The kernels of ns_kernels.hip; all take (const NsArgs a).  The row kernels: grid = nrows, kNsWave threads.
 enum NsKernel {
     kNsStart,         // U = Y = U0, counters 0, no direction, no stamp
-    kNsStarted,       // after logL(Y): L = logL(U0); status -1 for a start outside the cube, with a NaN or not above Lmin
+    kNsStarted,       // after logL(Y): L = logL(U0) (+ lnprior(U0) under a Gaussian prior); status -1 for a start outside the cube, with a NaN or not above Lmin
     kNsStep,          // decide on the trial of step it - 1 (its logL at LY[slot ? slot[row] : row]), propose the trial of step
                       // it and stamp the row with it
     kNsPack,          // ONE workgroup of kNsPackBlock threads: the rows stamped `it`, ascending, into idx / slot; their count

@@ -12,6 +12,9 @@
 // file (hipcc contracts by default, and HIP's __dmul_rn / __dadd_rn are plain operators that it contracts all the same), so
 // that numpy restates a trajectory exactly (tests/ns_reference.py).  A finished row (status != 0) is carried: its point, its
 // logL and its counters stay as they are and its trial row is its own point.
+// Under a Gaussian prior (mcalf_set_gauss_prior; a.prior.mu != NULL) the constrained quantity is logL + lnprior, one rounded
+// add of the launch's logL and row_lnprior (prior_device.h) of the row the wave holds: the start's in the started kernel, the
+// trial's in the step kernel's decide; it is what goes into L.  Without one the code path is the one without the branch.
 // Packing (mcalf_set_slice_compact): a row that proposes stamps itself with the step; the pack kernel lists the stamped rows in
 // row order (integers only), the gather kernel copies their trial rows together for a logL launch over those alone, and the
 // step kernel reads a trial's logL through the row's slot.  No row's bits depend on it.
@@ -21,6 +24,7 @@
 
 #pragma clang fp contract(off)
 
+#include "prior_device.h"
 #include "wave_row.h"
 
 using namespace mcalf;
@@ -52,7 +56,8 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_started_kernel(const NsAr
         const double v = a.U0[o + k];
         bad |= outside_unit(v);
     }
-    const double l = a.LY[row];
+    double l = a.LY[row];
+    if (a.prior.mu) l = l + row_lnprior(a.prior, a.U0 + o, 1);   // (one rounded add; every lane of the wave is here)
     const bool outside = __any(bad);
     if (lane != 0) return;
     a.L[row] = l;
@@ -68,7 +73,8 @@ __global__ __launch_bounds__(kNsWave) void mcalf_slice_step_kernel(const NsArgs 
     double tl = a.brk[row], tr = a.brk[n + row];
     int dir = __builtin_amdgcn_readfirstlane(a.dir[row]);
     if (a.decide) {
-        const double ly = a.LY[a.slot ? a.slot[row] : row];
+        double ly = a.LY[a.slot ? a.slot[row] : row];
+        if (a.prior.mu) ly = ly + row_lnprior(a.prior, y, 1);  // (LY by slot, the trial row by row)
         if (ly > a.Lmin[row]) {                                // accepted: the trial row stays the row's own point
             for (int k = lane; k < a.ndim; k += kNsWave) x[k] = y[k];
             const int mv = a.moves[row] + 1;

@@ -1,7 +1,8 @@
 """Ensemble MCMC on top of a batched walker step: the book-keeping of a run in numpy on the host, the likelihood work behind
 two callables.
 
-    loglike_cube(U) -> (theta, logL)                       rows of the unit cube in, transformed rows and logL out
+    loglike_cube(U) -> (theta, logL[, lnprior])            rows of the unit cube in, transformed rows and logL out (and lnprior of
+                                                           the rows, where the target has a prior beyond the flat cube)
     advance(U0, nsteps, thin, seed, first_iter, chain)
         -> (U, theta, logL, status, naccept, chainU, chainL)
                                                            the walkers U0 [n, ndim] moved by `nsteps` iterations; with `chain`
@@ -55,11 +56,15 @@ class EnsembleResult:
     """What `ensemble_sample` returns.
 
     cube, theta, logL     the kept chain, [nkeep, nwalkers, ndim] twice and [nkeep, nwalkers]
+    lnprior               lnprior of the kept rows [nkeep, nwalkers] where `loglike_cube` returns it as a third array (one pass
+                          over the rows already transformed), else None; logL is the likelihood's in either case
     accept_frac           accepted proposals per walker over the nsteps iterations after burn-in, / nsteps (one proposal per
                           walker and iteration) [nwalkers]
     status                0, or -1 for a walker whose start lay outside the cube or had a NaN (it never moved) [nwalkers]
     last                  the walkers after the last iteration [nwalkers, ndim] (continue with first_iter = burn + nsteps)
     nwalkers, nsteps, burn, thin, seed"""
+
+    lnprior = None
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -101,6 +106,8 @@ def ensemble_sample(loglike_cube, advance, ndim, nwalkers, nsteps, burn=0, thin=
     U, _, _, status, naccept, CU, CL = advance(np.ascontiguousarray(U), nsteps, thin=thin, seed=seed, first_iter=burn, chain=True)
     nkeep = nsteps // thin
     CU, CL = np.asarray(CU, dtype=float).reshape(nkeep, n, ndim), np.asarray(CL, dtype=float).reshape(nkeep, n)
-    theta = np.asarray(loglike_cube(CU.reshape(-1, ndim))[0], dtype=float).reshape(nkeep, n, -1) if nkeep else np.empty((0, n, ndim))
-    return EnsembleResult(cube=CU, theta=theta, logL=CL, accept_frac=np.asarray(naccept) / max(nsteps, 1), status=np.asarray(status),
+    out = loglike_cube(CU.reshape(-1, ndim)) if nkeep else (np.empty((0, n, ndim)),)
+    theta = np.asarray(out[0], dtype=float).reshape(nkeep, n, -1 if nkeep else ndim)
+    extra = dict(lnprior=np.asarray(out[2], dtype=float).reshape(nkeep, n)) if len(out) > 2 else {}
+    return EnsembleResult(cube=CU, theta=theta, logL=CL, **extra, accept_frac=np.asarray(naccept) / max(nsteps, 1), status=np.asarray(status),
                           last=np.asarray(U), nwalkers=n, nsteps=nsteps, burn=burn, thin=thin, seed=seed)

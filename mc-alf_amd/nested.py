@@ -27,9 +27,13 @@ class NestedResult:
     unfinished            rows a replacement call returned with status 0 (kept: they satisfy their constraint)
     rows_launched         rows handed to likelihood launches, carried finished rows included (None: the `replace` callable does
                           not say; `als_fitter.nested_sample` fills it in from `slice_stats()`)
+    lnprior               lnprior of the dead points [n] under a Gaussian prior (None: the callables do not say;
+                          `als_fitter.nested_sample` fills it in when one is set -- its callables then return logL + lnprior,
+                          so `logL` holds that sum and logZ is ln of the integral of L g over the cube)
     nlive"""
 
     rows_launched = None
+    lnprior = None
 
     def __init__(self, **kw):
         self.__dict__.update(kw)

@@ -106,6 +106,26 @@ def _read_ascii_table(path, coldef):
     return data[:, idx[0]], data[:, idx[1]], data[:, idx[2]]
 
 
+def parse_gpriors(Gpriors, ndim):
+    """(mu, sigma) [ndim] of the reference's `Gpriors` keyword (hires_fitter.py:34, :225-230): a flat sequence of 2 ndim entries
+    `[val_0, sig_0, val_1, sig_1, ...]`, each a number or the string 'none'; a pair with either entry 'none' carries no Gaussian
+    (sigma 0, mu 0).  None -> None."""
+    if Gpriors is None:
+        return None
+    g = list(Gpriors)
+    if len(g) != 2 * ndim:
+        raise ValueError(f"Gpriors must have 2 * ndim = {2 * ndim} entries [val_0, sig_0, val_1, sig_1, ...], got {len(g)}")
+    mu, sigma = np.zeros(ndim), np.zeros(ndim)
+    for k in range(ndim):
+        val, sig = g[2 * k], g[2 * k + 1]
+        if (isinstance(val, str) and val == 'none') or (isinstance(sig, str) and sig == 'none'):
+            continue
+        mu[k], sigma[k] = float(val), float(sig)
+        if not sigma[k] > 0.0:
+            raise ValueError(f"Gpriors: the width of parameter {k} must be > 0 (or 'none'), got {sig!r}")
+    return mu, sigma
+
+
 class als_fitter:
     """Drop-in for `mcalf.routines.hires_fitter.als_fitter` (hires_fitter.py:30).
 
@@ -189,6 +209,7 @@ class als_fitter:
         self.ndim = len(self.bounds)
         self._lo = np.array([np.min(b) for b in self.bounds], dtype=float)
         self._hi = np.array([np.max(b) for b in self.bounds], dtype=float)
+        self._gauss = parse_gpriors(Gpriors, self.ndim)     # (mu, sigma) for the device, sent with the first _ensure_prior
 
         # Asymmetric-veto thresholds (hires_fitter.py:179-181): counts of a standard-normal draw
         # above 3, 4, 5 sigma.  The reference's draw is unseeded; pass gauss_cdf=[n3, n4, n5] to pin it.
@@ -491,6 +512,81 @@ class als_fitter:
             _lib.check(self._lib.mcalf_set_prior(self._ctx, self._lo.ctypes.data_as(pd),
                                                  self._hi.ctypes.data_as(pd), int(key)), self._ctx)
             self._prior_key = key
+        if self._gauss is not None and not getattr(self, "_gauss_sent", False):
+            mu, sigma = self._gauss
+            _lib.check(self._lib.mcalf_set_gauss_prior(self._ctx, self._ptr(mu), self._ptr(sigma)), self._ctx)
+            self._gauss_sent = True
+
+    def set_gauss_prior(self, mu, sigma):
+        """Gaussian prior factors on top of the box (`mcalf_set_gauss_prior`): parameter k carries
+        exp(-0.5 ((theta_k - mu[k]) / sigma[k])^2) / sqrt(2 pi sigma[k]^2) where sigma[k] > 0 and none where sigma[k] == 0, not
+        renormalised for the truncation by the box (hires_fitter.py:230).  `lnprior_batch`, `slice_replace_batch` /
+        `nested_sample`, `ensemble_batch` / `ensemble_sample` and `tempered_batch` / `tempered_sample` honour it;
+        `maximize_batch` does not.  The ncomp slot cannot carry one."""
+        mu = np.ascontiguousarray(mu, dtype=float).reshape(-1)
+        sigma = np.ascontiguousarray(sigma, dtype=float).reshape(-1)
+        if mu.size != self.ndim or sigma.size != self.ndim:
+            raise ValueError(f"mu and sigma must have ndim = {self.ndim} entries, got {mu.size} and {sigma.size}")
+        self._gauss = None                                   # (what the constructor parsed is superseded)
+        self._ensure_prior()
+        _lib.check(self._lib.mcalf_set_gauss_prior(self._ctx, self._ptr(mu), self._ptr(sigma)), self._ctx)
+
+    def clear_gauss_prior(self):
+        """Back to the flat box: every entry runs the code path, and returns the bits, of a fitter that never had a Gaussian."""
+        self._gauss = None
+        self._ensure_prior()
+        _lib.check(self._lib.mcalf_set_gauss_prior(self._ctx, None, None), self._ctx)
+
+    @property
+    def gauss_prior(self):
+        """(mu, sigma, c) [ndim] as the library holds them (`mcalf_get_gauss_prior`), c[k] = ln(2 pi sigma[k]^2) as the kernels
+        add it; None when no Gaussian is set."""
+        self._ensure_prior()
+        mu, sigma, c = (np.empty(self.ndim) for _ in range(3))
+        n = C.c_int32(0)
+        _lib.check(self._lib.mcalf_get_gauss_prior(self._ctx, self._ptr(mu), self._ptr(sigma), self._ptr(c), C.byref(n)), self._ctx)
+        return (mu, sigma, c) if n.value > 0 else None
+
+    def lnprior_batch(self, rows, cube=False):
+        """lnprior[i] of every row on the device (`mcalf_lnprior_batch`; a HIP kernel): -inf for a row with a NaN or an entry
+        outside the box, else the sum of the Gaussian factors' logarithms (hires_fitter.py:218-234), an exact 0 without any.
+        `cube=True`: the rows are unit-cube rows, mapped through the box as `loglike_cube_batch` maps them."""
+        rows = self._rows(rows, self.ndim)
+        self._ensure_prior()
+        out = np.empty(rows.shape[0])
+        _lib.check(self._lib.mcalf_lnprior_batch(self._ctx, self._ptr(rows), rows.shape[0], int(bool(cube)), self._ptr(out)), self._ctx)
+        return out
+
+    def lnprior(self, p):
+        """hires_fitter.py:218-234."""
+        return float(self.lnprior_batch(np.asarray(p, dtype=float))[0])
+
+    def __call__(self, p):
+        """hires_fitter.py:509-518: lnprior + lnlhood with the reference's two -inf short cuts (the reference names a method
+        `lnlhood` that does not exist; this calls `lnlhood_worker`)."""
+        lp = self.lnprior(p)
+        if not np.isfinite(lp):
+            return -np.inf
+        lh = self.lnlhood_worker(p)
+        if not np.isfinite(lh):
+            return -np.inf
+        return lh + lp
+
+    def _cube_posterior(self, U):
+        """(theta, logL + lnprior) of unit-cube rows: the callable the host drivers start from."""
+        theta, logL = self.loglike_cube_batch(U)
+        return (theta, logL + self.lnprior_batch(U, cube=True)) if self._has_gauss() else (theta, logL)
+
+    def _cube_with_prior(self, U):
+        """(theta, logL, lnprior) of unit-cube rows, lnprior by one pass over the rows already transformed."""
+        theta, logL = self.loglike_cube_batch(U)
+        return theta, logL, self.lnprior_batch(theta)
+
+    def _has_gauss(self):
+        self._ensure_prior()
+        n = C.c_int32(0)
+        _lib.check(self._lib.mcalf_get_gauss_prior(self._ctx, None, None, None, C.byref(n)), self._ctx)
+        return n.value > 0
 
     def maximize_batch(self, P0, max_iter=50, cg_iters=None, lambda0=1e-3, ftol=1e-10, rows_per_block=0):
         """(P, logL, status, niter): every row of P0 polished to a maximum of logL inside the prior box by a batched
@@ -503,7 +599,8 @@ class als_fitter:
         below the clamped start's.  status: 1 converged (the last accepted gain is <= ftol (1 + |logL|)), 0 `max_iter`
         reached, 2 zero projected gradient, 3 damping beyond 1e12, -1 the start's logL is not finite (the row comes
         back as given).  niter: outer iterations the row took a step in.  `rows_per_block` bounds the rows fitted together
-        (0: the library's rule); a row's result does not depend on it."""
+        (0: the library's rule); a row's result does not depend on it.  A Gaussian prior (`set_gauss_prior`) does not enter:
+        the fit maximises logL alone."""
         P0 = self._rows(P0, self.ndim)
         n = P0.shape[0]
         self._ensure_prior()
@@ -537,7 +634,11 @@ class als_fitter:
         -1 the start lies outside the cube, has a NaN or does not satisfy the constraint (the row comes back as given).
         nevals: trials the row evaluated; moves: accepted ones.  The random words of a row are Philox4x64-10 of (step,
         stream_ids[row], seed) -- `stream_ids` (None: arange) must be distinct -- so a row's result does not depend on its
-        batch or its position."""
+        batch or its position.
+
+        Under a Gaussian prior (`Gpriors`, `set_gauss_prior`) the constrained quantity is logL + lnprior, evaluated inside the
+        step's own kernels: `Lmin` bounds that sum and logL[i] is `loglike_cube_batch(U)[i] + lnprior_batch(U, cube=True)[i]`
+        bit for bit."""
         U0 = self._rows(U0, self.ndim)
         n = U0.shape[0]
         dirs = self._rows(dirs, self.ndim)
@@ -578,7 +679,9 @@ class als_fitter:
         Returns a `nested.NestedResult`: logZ, logZ_err, H, the dead points with their log weights, and
         `equal_weight_samples(rng)`, whose output goes into `write_equal_weights`.  Its `rows_launched` counts the rows
         handed to likelihood launches: nlive for the initial points and `slice_stats()["rows_launched"]` of every round
-        (`set_slice_compact(True)` lowers it; nothing else of the result depends on that setting)."""
+        (`set_slice_compact(True)` lowers it; nothing else of the result depends on that setting).  Under a Gaussian prior
+        (`Gpriors`, `set_gauss_prior`) both entries work on logL + lnprior: nested sampling of L g under the box measure, so
+        `logL` holds that sum, `lnprior` the prior's part, and logZ is ln of the integral of L g over the cube."""
         from .. import nested
         launched = [int(nlive)]
 
@@ -587,9 +690,12 @@ class als_fitter:
             launched[0] += self.slice_stats()["rows_launched"]
             return out
 
-        res = nested.nested_sample(lambda U: self.loglike_cube_batch(U), replace, self.ndim, nlive, batch=batch, nmoves=nmoves,
-                                   dlogz=dlogz, max_rounds=max_rounds, seed=seed)
+        gauss = self._has_gauss()
+        res = nested.nested_sample(self._cube_posterior if gauss else (lambda U: self.loglike_cube_batch(U)), replace, self.ndim, nlive, batch=batch,
+                                   nmoves=nmoves, dlogz=dlogz, max_rounds=max_rounds, seed=seed)
         res.rows_launched = launched[0]
+        if gauss:
+            res.lnprior = self.lnprior_batch(res.cube, cube=True)
         return res
 
     def ensemble_batch(self, U0, nsteps, thin=1, move="stretch", scale=None, seed=0, first_iter=0, chain=True):
@@ -605,7 +711,11 @@ class als_fitter:
         proposals per walker.  chainU [nsteps // thin, nwalkers, ndim] and chainL [nsteps // thin, nwalkers] hold the state
         after every thin-th iteration, kept on the device until the call ends (`chain=False`: None, None).  The random words
         are Philox4x64-10 of (half-step, walker, seed): calling again with the returned U and `first_iter` advanced by
-        `nsteps` is, bit for bit, the longer call."""
+        `nsteps` is, bit for bit, the longer call.
+
+        Under a Gaussian prior (`Gpriors`, `set_gauss_prior`) the target is logL + lnprior: the accept rule gains
+        lnprior(trial) - lnprior(walker), evaluated inside the step's own kernels, while logL and chainL stay the likelihood's
+        (`lnprior_batch(U, cube=True)` gives the prior's part)."""
         U0 = self._rows(U0, self.ndim)
         n = U0.shape[0]
         moves = {"stretch": _lib.MCALF_ENS_STRETCH, "de": _lib.MCALF_ENS_DE}
@@ -638,7 +748,7 @@ class als_fitter:
         def advance(U0, nsteps, thin=1, seed=0, first_iter=0, chain=True):
             return self.ensemble_batch(U0, nsteps, thin=thin, move=move, scale=scale, seed=seed, first_iter=first_iter, chain=chain)
 
-        return ensemble.ensemble_sample(lambda U: self.loglike_cube_batch(U), advance, self.ndim, nwalkers, nsteps, burn=burn, thin=thin,
+        return ensemble.ensemble_sample(self._cube_with_prior if self._has_gauss() else (lambda U: self.loglike_cube_batch(U)), advance, self.ndim, nwalkers, nsteps, burn=burn, thin=thin,
                                         start=start, ball=ball, seed=seed)
 
     def tempered_batch(self, U0, betas, nsteps, thin=1, swap_every=1, move="stretch", scale=None, seed=0, first_iter=0, chain=True, chain_temps=1):
@@ -655,7 +765,11 @@ class als_fitter:
         chainL [nsteps // thin, T, nwalkers] keeps logL of every rung (the evidence needs them), chainU
         [nsteps // thin, chain_temps, nwalkers, ndim] the rows of the first `chain_temps` rungs (`chain=False`: None, None).
         The random words are Philox4x64-10 of (half-step or swap round, position, seed): calling again with the returned U and
-        `first_iter` advanced by `nsteps` is, bit for bit, the longer call, and one rung at beta = 1 is `ensemble_batch`."""
+        `first_iter` advanced by `nsteps` is, bit for bit, the longer call, and one rung at beta = 1 is `ensemble_batch`.
+
+        Under a Gaussian prior (`Gpriors`, `set_gauss_prior`) rung t samples logL^betas[t] times the prior's Gaussian factors:
+        the temperature acts on logL alone, the swap rule is unchanged (the prior cancels between rungs), and the rung at
+        beta = 0 samples the Gaussian factors over the cube; logL and chainL stay the likelihood's."""
         U0 = np.ascontiguousarray(U0, dtype=float)
         betas = np.ascontiguousarray(betas, dtype=float).reshape(-1)
         T = betas.size
@@ -690,7 +804,9 @@ class als_fitter:
         ends at the prior) is the ladder; every rung holds `nwalkers` walkers, started uniformly in the cube or in a ball of
         half-width `ball` around the cube point `start`.  Returns a `tempering.TemperedResult`: logL of every rung, the
         acceptance and swap fractions per rung, `cold()` -- the beta[0] rung as an `ensemble.EnsembleResult` -- and the
-        evidence by `logZ_stepping_stone()` and `logZ_ti()`."""
+        evidence by `logZ_stepping_stone()` and `logZ_ti()`.  Under a Gaussian prior the result carries `ln_prior_mass`, the
+        ladder's Z at beta = 0, which both evidence routes add: they then report ln of the integral of L g over the cube, as
+        `nested_sample` does."""
         from .. import tempering
         betas = tempering.default_ladder(ntemps, 1e-4) if betas is None else betas
 
@@ -698,8 +814,13 @@ class als_fitter:
             return self.tempered_batch(U0, betas, nsteps, thin=thin, swap_every=swap_every, move=move, scale=scale, seed=seed, first_iter=first_iter,
                                        chain=chain, chain_temps=chain_temps)
 
-        return tempering.tempered_sample(lambda U: self.loglike_cube_batch(U), advance, self.ndim, nwalkers, nsteps, betas, burn=burn, thin=thin,
-                                         swap_every=swap_every, start=start, ball=ball, seed=seed)
+        gauss = self._has_gauss()
+        res = tempering.tempered_sample(self._cube_with_prior if gauss else (lambda U: self.loglike_cube_batch(U)), advance, self.ndim, nwalkers, nsteps, betas,
+                                        burn=burn, thin=thin, swap_every=swap_every, start=start, ball=ball, seed=seed)
+        if gauss:
+            mu, sigma, _ = self.gauss_prior
+            res.ln_prior_mass = tempering.ln_prior_mass(self._lo, self._hi, mu, sigma)
+        return res
 
     def loglike_hvp_batch(self, P, V, out=None):
         """HV[i, :] = H(P[i]) V[i, :] with H = d2 logL / dtheta2, the exact Hessian of `lnlhood_worker` under the context's

@@ -36,6 +36,19 @@ def default_ladder(ntemps, beta_min):
     return beta
 
 
+def ln_prior_mass(lo, hi, mu, sigma):
+    """ln of the integral over the unit cube of the Gaussian prior factors g (not renormalised for the box): the sum over the
+    coordinates with sigma[k] > 0 of ln((Phi((hi_k - mu_k) / sigma_k) - Phi((lo_k - mu_k) / sigma_k)) / (hi_k - lo_k)), Phi the
+    standard normal distribution function by `math.erf`.  It is ln Z(beta = 0) of a ladder under such a prior; 0.0 with none."""
+    import math                                             # (the standard library's erf: the module stays numpy and `ensemble`)
+    total = 0.0
+    for l, h, m, s in zip(np.asarray(lo, dtype=float), np.asarray(hi, dtype=float), np.asarray(mu, dtype=float), np.asarray(sigma, dtype=float)):
+        if s > 0.0:
+            a, b = (l - m) / (s * math.sqrt(2.0)), (h - m) / (s * math.sqrt(2.0))
+            total += math.log(0.5 * (math.erf(b) - math.erf(a)) / (h - l))
+    return total
+
+
 class TemperedResult:
     """What `tempered_sample` returns.
 
@@ -48,7 +61,12 @@ class TemperedResult:
     status                0, or -1 for a position whose start lay outside the cube or had a NaN (it never moved nor swapped)
                           [T, nwalkers]
     last                  the walkers after the last iteration [T, nwalkers, ndim] (continue with first_iter = burn + nsteps)
+    ln_prior_mass         None, or under a Gaussian prior ln of the integral of its factors over the cube (`ln_prior_mass`):
+                          the ladder then measures Z(1) / Z(0) with Z(0) this mass, and both evidence routes add it, so that
+                          they report ln of the integral of L g over the cube, as nested sampling of L g does
     nwalkers, nsteps, burn, thin, swap_every, seed"""
+
+    ln_prior_mass = None
 
     def __init__(self, loglike_cube, **kw):
         self._loglike_cube = loglike_cube
@@ -58,8 +76,10 @@ class TemperedResult:
         """The beta[0] rung as an `ensemble.EnsembleResult`; its theta comes from one `loglike_cube` pass over the kept cold
         rows alone.  Its `flat()` goes into `write_equal_weights`, `model_band_batch` and `eqw_batch`."""
         nkeep, n, ndim = self.cube.shape
-        theta = np.asarray(self._loglike_cube(self.cube.reshape(-1, ndim))[0], dtype=float).reshape(nkeep, n, -1) if nkeep else np.empty((0, n, ndim))
-        return EnsembleResult(cube=self.cube, theta=theta, logL=np.ascontiguousarray(self.logL[:, 0, :]), accept_frac=self.naccept[0] / max(self.nsteps, 1),
+        out = self._loglike_cube(self.cube.reshape(-1, ndim)) if nkeep else (np.empty((0, n, ndim)),)
+        theta = np.asarray(out[0], dtype=float).reshape(nkeep, n, -1 if nkeep else ndim)
+        extra = dict(lnprior=np.asarray(out[2], dtype=float).reshape(nkeep, n)) if len(out) > 2 else {}
+        return EnsembleResult(cube=self.cube, theta=theta, **extra, logL=np.ascontiguousarray(self.logL[:, 0, :]), accept_frac=self.naccept[0] / max(self.nsteps, 1),
                               status=self.status[0], last=self.last[0], nwalkers=n, nsteps=self.nsteps, burn=self.burn, thin=self.thin, seed=self.seed)
 
     def _rung(self, t, lo=0, hi=None):
@@ -85,6 +105,8 @@ class TemperedResult:
         if nbatch < 2 or size < 1:
             raise ValueError(f"{self.logL.shape[0]} kept iterations cannot be cut into {nbatch} batches")
         parts = np.array([self._stepping_stone(b * size, (b + 1) * size) for b in range(nbatch)])
+        if self.ln_prior_mass is not None:                  # (a Gaussian prior: Z(0) is its mass over the cube, a constant)
+            return self._stepping_stone() + self.ln_prior_mass, float(parts.std(ddof=1) / np.sqrt(nbatch))
         return self._stepping_stone(), float(parts.std(ddof=1) / np.sqrt(nbatch))
 
     def logZ_ti(self):
@@ -93,6 +115,8 @@ class TemperedResult:
         if self.betas[-1] != 0.0:
             raise ValueError(f"thermodynamic integration needs a ladder that ends at beta = 0 (the prior), got {self.betas[-1]}")
         mean = np.array([self._rung(t).mean() for t in range(self.betas.size)])
+        if self.ln_prior_mass is not None:
+            return float((0.5 * (mean[:-1] + mean[1:]) * (self.betas[:-1] - self.betas[1:])).sum()) + self.ln_prior_mass
         return float((0.5 * (mean[:-1] + mean[1:]) * (self.betas[:-1] - self.betas[1:])).sum())
 
 

@@ -11,7 +11,9 @@ Per run and move, on the same walkers:
           `loglike_cube_batch`, one host round trip per half-step (wall clock, --iters iterations, median of 3 calls).
 The device route and the numpy route must agree bit for bit over the first call (exit status 1 otherwise).  No ratio is fixed
 in advance.  One JSON line, also written to --out.
-python tools/ens_timing.py [--runs C:4096,B:1024] [--iters 4] [--reps 20] [--warmup 3] [--burn 20] [--out profiles/ens_timing.json]"""
+python tools/ens_timing.py [--runs C:4096,B:1024] [--iters 4] [--reps 20] [--warmup 3] [--burn 20] [--gauss] [--out profiles/ens_timing.json]
+--gauss: the same runs under a Gaussian prior on four coordinates (mcalf_set_gauss_prior); the numpy route is then
+tests/prior_reference.py's."""
 import argparse
 import ctypes as C
 import json
@@ -27,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mcalf_amd  # noqa: E402
 import ens_reference as er  # noqa: E402
+import prior_reference as prr  # noqa: E402
 from mcalf_amd import _lib, workloads  # noqa: E402
 
 MOVES = {"stretch": er.STRETCH, "de": er.DE}
@@ -77,6 +80,15 @@ class _Device:
         return self._timed(two)
 
 
+def _set_gauss(fit):
+    """--gauss: a Gaussian prior on the four coordinates behind the ncomp slot, centred on the middle of the box, a quarter of
+    the box wide."""
+    mu, sigma = np.zeros(fit.ndim), np.zeros(fit.ndim)
+    k = slice(fit.startind + 1, fit.startind + 5)
+    mu[k], sigma[k] = 0.5 * (fit._lo[k] + fit._hi[k]), 0.25 * (fit._hi[k] - fit._lo[k])
+    fit.set_gauss_prior(mu, sigma)
+
+
 def _run(fit, n, move, seed, args):
     logl = lambda U: fit.loglike_cube_batch(U, return_theta=False)
     rng = np.random.default_rng(seed)
@@ -91,7 +103,10 @@ def _run(fit, n, move, seed, args):
     t_np = []
     for _ in range(3):
         t0 = time.perf_counter()
-        ref = er.ensemble(logl, U, args.iters, args.iters, MOVES[move], None, seed, it)
+        if args.gauss:
+            ref = prr.ensemble(logl, lambda Y: fit.lnprior_batch(Y, cube=True), U, args.iters, args.iters, MOVES[move], None, seed, it)
+        else:
+            ref = er.ensemble(logl, U, args.iters, args.iters, MOVES[move], None, seed, it)
         t_np.append((time.perf_counter() - t0) * 1e3 / args.iters)
     same = np.array_equal(got[0], ref[0]) and got[1].tobytes() == ref[1].tobytes() and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3])
     t_dev, t_bare, acc = [], [], []
@@ -118,13 +133,16 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--burn", type=int, default=20)
+    ap.add_argument("--gauss", action="store_true", help="a Gaussian prior on four coordinates (mcalf_set_gauss_prior)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    out, same = {"iterations_per_call": args.iters, "reps": args.reps, "warmup": args.warmup, "burn": args.burn, "runs": []}, True
+    out, same = {"gauss": args.gauss, "iterations_per_call": args.iters, "reps": args.reps, "warmup": args.warmup, "burn": args.burn, "runs": []}, True
     for run in args.runs.split(","):
         name, n = run.split(":")
         kw, _, seed = workloads.config(name, _synth)
         with mcalf_amd.als_fitter(None, **kw) as fit:
+            if args.gauss:
+                _set_gauss(fit)
             for move in MOVES:
                 row, ok = _run(fit, int(n), move, seed, args)
                 same &= ok

@@ -14,7 +14,9 @@ Recorded per round: lock steps, ms per step and per round of each route, the row
 and the trials (`slice_stats`), and the lock-step waste -- the share of evaluated rows that were already finished,
 1 - sum(nevals) / (steps K).  Per run: the median over the timed rounds, and their minimum and maximum.  The routes must agree
 bit for bit (exit status 1 otherwise).  One JSON line, also written to --out.
-python tools/ns_timing.py [--configs C,B] [--chains 1024,4096] [--rounds 5] [--burn 20] [--nmoves 8] [--max-steps 400] [--out profiles/ns_timing.json]"""
+python tools/ns_timing.py [--configs C,B] [--chains 1024,4096] [--rounds 5] [--burn 20] [--nmoves 8] [--max-steps 400] [--gauss] [--out profiles/ns_timing.json]
+--gauss: the same runs under a Gaussian prior on four coordinates (mcalf_set_gauss_prior); the numpy route is then
+tests/prior_reference.py's."""
 import argparse
 import ctypes as C
 import json
@@ -60,9 +62,21 @@ def _device_entry_ms(fit, U0, lmin, D, sid, nmoves, steps, seed):
     return a.elapsed_time(b), (dU.cpu().numpy(), dL.cpu().numpy(), dS.cpu().numpy(), dN.cpu().numpy(), dM.cpu().numpy())
 
 
-def _run(fit, K, rounds, nmoves, max_steps, seed, burn):
+def _set_gauss(fit):
+    """--gauss: a Gaussian prior on the four coordinates behind the ncomp slot, centred on the middle of the box, a quarter of
+    the box wide."""
+    mu, sigma = np.zeros(fit.ndim), np.zeros(fit.ndim)
+    k = slice(fit.startind + 1, fit.startind + 5)
+    mu[k], sigma[k] = 0.5 * (fit._lo[k] + fit._hi[k]), 0.25 * (fit._hi[k] - fit._lo[k])
+    fit.set_gauss_prior(mu, sigma)
+
+
+def _run(fit, K, rounds, nmoves, max_steps, seed, burn, gauss=False):
     rng = np.random.default_rng(seed)
     nlive, logl = 4 * K, (lambda U: fit.loglike_cube_batch(U, return_theta=False))
+    if gauss:                                         # (the constrained quantity: logL + lnprior, one rounded add)
+        like = logl
+        logl = lambda U: like(U) + fit.lnprior_batch(U, cube=True)
     U = rng.random((nlive, fit.ndim))
     L = logl(U)
     rows, next_id, same = [], 0, True
@@ -129,14 +143,17 @@ def main():
     ap.add_argument("--burn", type=int, default=20)
     ap.add_argument("--nmoves", type=int, default=8)
     ap.add_argument("--max-steps", type=int, default=400)
+    ap.add_argument("--gauss", action="store_true", help="a Gaussian prior on four coordinates (mcalf_set_gauss_prior)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    out, same = {"nmoves": args.nmoves, "max_steps": args.max_steps, "burn_rounds": args.burn, "runs": []}, True
+    out, same = {"gauss": args.gauss, "nmoves": args.nmoves, "max_steps": args.max_steps, "burn_rounds": args.burn, "runs": []}, True
     for name in args.configs.split(","):
         kw, _, seed = workloads.config(name, _synth)
         with mcalf_amd.als_fitter(None, **kw) as fit:
+            if args.gauss:
+                _set_gauss(fit)
             for K in (int(k) for k in args.chains.split(",")):
-                rows, med, spread, ok = _run(fit, K, args.rounds, args.nmoves, args.max_steps, seed, args.burn)
+                rows, med, spread, ok = _run(fit, K, args.rounds, args.nmoves, args.max_steps, seed, args.burn, args.gauss)
                 same &= ok
                 out["runs"].append({"config": name, "npix": int(fit.obj_wl.size), "ndim": int(fit.ndim), "chains": K, "nlive": 4 * K,
                                     "routes_agree_bit_for_bit": ok, "median_over_rounds": med, "min_max_over_rounds": spread, "rounds": rows})

@@ -12,7 +12,9 @@ Per run and move, on the same walkers, between HIP events on one stream, ms per 
             offered before.
 The first timed call of `swaps` must equal the numpy restatement (tests/pt_reference.py around `loglike_cube_batch`) bit for bit
 (exit status 1 otherwise).  No ratio is fixed in advance.  One JSON line, also written to --out.
-python tools/pt_timing.py [--runs C:8x512,B:4x256] [--moves stretch] [--iters 4] [--reps 20] [--warmup 3] [--burn 20] [--out profiles/pt_timing.json]"""
+python tools/pt_timing.py [--runs C:8x512,B:4x256] [--moves stretch] [--iters 4] [--reps 20] [--warmup 3] [--burn 20] [--gauss] [--out profiles/pt_timing.json]
+--gauss: the same runs under a Gaussian prior on four coordinates (mcalf_set_gauss_prior); the numpy route is then
+tests/prior_reference.py's."""
 import argparse
 import ctypes as C
 import json
@@ -28,6 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mcalf_amd  # noqa: E402
 import ens_reference as er  # noqa: E402
 import pt_reference as pr  # noqa: E402
+import prior_reference as prr  # noqa: E402
 from mcalf_amd import _lib, tempering, workloads  # noqa: E402
 
 MOVES = {"stretch": er.STRETCH, "de": er.DE}
@@ -96,6 +99,15 @@ class _Device:
         return self._timed(two)
 
 
+def _set_gauss(fit):
+    """--gauss: a Gaussian prior on the four coordinates behind the ncomp slot, centred on the middle of the box, a quarter of
+    the box wide."""
+    mu, sigma = np.zeros(fit.ndim), np.zeros(fit.ndim)
+    k = slice(fit.startind + 1, fit.startind + 5)
+    mu[k], sigma[k] = 0.5 * (fit._lo[k] + fit._hi[k]), 0.25 * (fit._hi[k] - fit._lo[k])
+    fit.set_gauss_prior(mu, sigma)
+
+
 def _run(fit, T, n, move, seed, args):
     logl = lambda U: fit.loglike_cube_batch(U, return_theta=False)
     betas = tempering.default_ladder(T, 1e-4)
@@ -108,7 +120,10 @@ def _run(fit, T, n, move, seed, args):
     it = args.burn
     # the first call: the device route and the numpy route on the same walkers
     _, got = dev.advance(U, args.iters, move, seed, it, 1)
-    ref = pr.tempered(logl, U, betas, args.iters, args.iters, 1, MOVES[move], None, seed, it, 0)
+    if args.gauss:
+        ref = prr.tempered(logl, lambda Y: fit.lnprior_batch(Y, cube=True), U, betas, args.iters, args.iters, 1, MOVES[move], None, seed, it, 0)
+    else:
+        ref = pr.tempered(logl, U, betas, args.iters, args.iters, 1, MOVES[move], None, seed, it, 0)
     same = np.array_equal(got[0], ref[0]) and got[1].tobytes() == ref[1].tobytes() and all(np.array_equal(got[k], ref[k]) for k in (2, 3, 4))
     t = {"swaps": [], "no_swaps": [], "bare": [], "separate": []}
     acc, swp = [], []
@@ -143,14 +158,17 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--burn", type=int, default=20)
+    ap.add_argument("--gauss", action="store_true", help="a Gaussian prior on four coordinates (mcalf_set_gauss_prior)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    out, same = {"iterations_per_call": args.iters, "reps": args.reps, "warmup": args.warmup, "burn": args.burn, "runs": []}, True
+    out, same = {"gauss": args.gauss, "iterations_per_call": args.iters, "reps": args.reps, "warmup": args.warmup, "burn": args.burn, "runs": []}, True
     for run in args.runs.split(","):
         name, shape = run.split(":")
         T, n = (int(v) for v in shape.split("x"))
         kw, _, seed = workloads.config(name, _synth)
         with mcalf_amd.als_fitter(None, **kw) as fit:
+            if args.gauss:
+                _set_gauss(fit)
             for move in args.moves.split(","):
                 row, ok = _run(fit, T, n, move, seed, args)
                 same &= ok
