@@ -187,9 +187,10 @@ MCALF_SLICE_MAXSTEPS, MCALF_SLICE_DONE, MCALF_SLICE_BAD_START = 0, 1, -1
 MCALF_FIT_MAXITER, MCALF_FIT_CONVERGED, MCALF_FIT_ZERO_GRADIENT, MCALF_FIT_LAMBDA, MCALF_FIT_BAD_START = 0, 1, 2, 3, -1
 
 
-# every symbol include/mcalf_hip.h declares: name -> (restype, argtypes)
-_PD = C.POINTER(C.c_double)
+# every symbol include/mcalf_hip.h declares: name -> (restype, argtypes).  Array arguments are void*: a plain address is
+# accepted, and so is a typed ctypes pointer made from `ndarray.ctypes`, whatever the element type in the header.
 _CTX = C.c_void_p
+_P = C.c_void_p            # a host or device array, or an options struct, by address
 SYMBOLS = {
     "mcalf_create": (C.c_int, [C.POINTER(mcalf_spec), C.POINTER(_CTX)]),
     "mcalf_create_multi": (C.c_int, [C.POINTER(mcalf_spec), C.POINTER(C.c_int32), C.c_int32, C.POINTER(_CTX)]),
@@ -204,74 +205,63 @@ SYMBOLS = {
     "mcalf_set_chunks": (C.c_int, [_CTX, C.c_int32]),
     "mcalf_get_chunks": (C.c_int32, [_CTX, C.c_int64]),
     # (host pointers as void*: plain addresses are accepted, which spares the hot wrappers two ctypes pointer objects per call)
-    "mcalf_loglike_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p]),
-    "mcalf_model_batch": (C.c_int, [_CTX, _PD, C.c_int64, C.c_int32, _PD]),
-    "mcalf_chi2_batch": (C.c_int, [_CTX, _PD, C.c_int64, _PD]),
-    "mcalf_onecomp_batch": (C.c_int, [_CTX, _PD, C.c_int64, C.c_int32, _PD]),
-    "mcalf_loglike_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mcalf_model_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "mcalf_loglike_grad_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mcalf_loglike_grad_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_loglike_hvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "mcalf_loglike_hvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mcalf_eqw_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
-    "mcalf_eqw_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_model_band_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_model_band_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_fisher_matvec_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "mcalf_fisher_matvec_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mcalf_maximize_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_maximize_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p]),
-    "mcalf_slice_replace_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_slice_replace_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p]),
+    "mcalf_loglike_batch": (C.c_int, [_CTX, _P, C.c_int64, _P]),
+    "mcalf_model_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P]),
+    "mcalf_chi2_batch": (C.c_int, [_CTX, _P, C.c_int64, _P]),
+    "mcalf_onecomp_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P]),
+    "mcalf_loglike_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P]),
+    "mcalf_model_batch_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, _P]),
+    "mcalf_loglike_grad_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P]),
+    "mcalf_loglike_grad_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P]),
+    "mcalf_loglike_hvp_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),
+    "mcalf_loglike_hvp_batch_device": (C.c_int, [_CTX, _P, _P, C.c_int64, _P, _P]),
+    "mcalf_eqw_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, _P]),
+    "mcalf_eqw_batch_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "mcalf_model_band_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
+    "mcalf_model_band_batch_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mcalf_fisher_matvec_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),
+    "mcalf_fisher_matvec_batch_device": (C.c_int, [_CTX, _P, _P, C.c_int64, _P, _P]),
+    "mcalf_maximize_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "mcalf_maximize_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "mcalf_slice_replace_batch": (C.c_int, [_CTX, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_slice_replace_batch_device": (C.c_int, [_CTX, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_set_slice_compact": (C.c_int, [_CTX, C.c_int32]),
     "mcalf_slice_last_stats": (C.c_int, [_CTX, C.POINTER(mcalf_slice_stats_t)]),
-    "mcalf_ensemble_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_ensemble_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_tempered_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_tempered_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_model_jvp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "mcalf_model_vjp_batch": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "mcalf_model_vjp_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mcalf_ensemble_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_ensemble_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_tempered_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_tempered_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_model_jvp_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),
+    "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, _P, _P, C.c_int64, _P, _P]),
+    "mcalf_model_vjp_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),
+    "mcalf_model_vjp_batch_device": (C.c_int, [_CTX, _P, _P, C.c_int64, _P, _P]),
     "mcalf_last_launch": (C.c_int, [_CTX, C.POINTER(mcalf_launch_info_t)]),
-    "mcalf_set_cu_mask": (C.c_int, [_CTX, C.POINTER(C.c_uint32), C.c_int32]),
+    "mcalf_set_cu_mask": (C.c_int, [_CTX, _P, C.c_int32]),
     "mcalf_stream_partition": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mcalf_profile_begin": (C.c_int, [_CTX, C.c_int32]),
     "mcalf_profile_end": (C.c_int, [_CTX, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
-    "mcalf_scale_cube_batch": (C.c_int, [_CTX, _PD, _PD, _PD, C.c_int64, C.c_int32, _PD]),
-    "mcalf_set_prior": (C.c_int, [_CTX, _PD, _PD, C.c_int32]),
-    "mcalf_loglike_cube_batch": (C.c_int, [_CTX, _PD, C.c_int64, _PD, _PD]),
-    "mcalf_loglike_cube_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mcalf_set_gauss_prior": (C.c_int, [_CTX, C.c_void_p, C.c_void_p]),
-    "mcalf_get_gauss_prior": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
-    "mcalf_lnprior_batch": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
-    "mcalf_lnprior_batch_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcalf_scale_cube_batch": (C.c_int, [_CTX, _P, _P, _P, C.c_int64, C.c_int32, _P]),
+    "mcalf_set_prior": (C.c_int, [_CTX, _P, _P, C.c_int32]),
+    "mcalf_loglike_cube_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P]),
+    "mcalf_loglike_cube_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P]),
+    "mcalf_set_gauss_prior": (C.c_int, [_CTX, _P, _P]),
+    "mcalf_get_gauss_prior": (C.c_int, [_CTX, _P, _P, _P, C.POINTER(C.c_int32)]),
+    "mcalf_lnprior_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P]),
+    "mcalf_lnprior_batch_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, _P]),
     "mcalf_set_resident": (C.c_int, [_CTX, C.c_int32]),
-    "mcalf_broker_serve_resident": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double]),
+    "mcalf_broker_serve_resident": (C.c_int, [_CTX, _P, C.c_int32, _P, C.c_int32, _P, C.c_double]),
     "mcalf_broker_serve": (C.c_int, [C.POINTER(_CTX), C.c_int32, C.POINTER(mcalf_broker_t), C.c_double]),
-    "mcalf_comm_unique_id": (C.c_int, [C.c_void_p]),
-    "mcalf_comm_init": (C.c_int, [_CTX, C.c_void_p, C.c_int32, C.c_int32]),
+    "mcalf_comm_unique_id": (C.c_int, [_P]),
+    "mcalf_comm_init": (C.c_int, [_CTX, _P, C.c_int32, C.c_int32]),
     "mcalf_comm_info": (C.c_int, [_CTX, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mcalf_comm_destroy": (C.c_int, [_CTX]),
     "mcalf_comm_set_overlap": (C.c_int, [_CTX, C.c_int32]),
-    "mcalf_comm_join": (C.c_int, [_CTX, C.c_void_p]),
-    "mcalf_loglike_gather_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
-    "mcalf_loglike_gatherv_device": (C.c_int, [_CTX, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
-                                               C.c_int32, C.c_void_p]),
-    "mcalf_voigt_hjerting": (C.c_int, [_PD, _PD, C.c_int64, _PD, C.c_int32]),
-    "mcalf_voigt_hjerting_nodes": (C.c_int, [_PD, _PD, C.c_int64, _PD, C.c_int32]),
-    "mcalf_voigt_hjerting_grad": (C.c_int, [_PD, _PD, C.c_int64, _PD, C.c_int32]),
+    "mcalf_comm_join": (C.c_int, [_CTX, _P]),
+    "mcalf_loglike_gather_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, C.c_int32, _P]),
+    "mcalf_loglike_gatherv_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, C.POINTER(C.c_int64), C.c_int32, _P]),
+    "mcalf_voigt_hjerting": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32]),
+    "mcalf_voigt_hjerting_nodes": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32]),
+    "mcalf_voigt_hjerting_grad": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32]),
 }
 
 _lib = None

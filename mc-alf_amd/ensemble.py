@@ -86,28 +86,47 @@ class EnsembleResult:
         return np.ascontiguousarray(self.logL[:, ok].reshape(-1)), np.ascontiguousarray(self.theta[:, ok, :].reshape(-1, self.theta.shape[2]))
 
 
+def _check_run(n, nsteps, burn, thin, swap_every=None):
+    """The run arguments of `ensemble_sample`, and of `tempering.tempered_sample` (which has `swap_every` as well)."""
+    if n < 4 or n % 2:
+        raise ValueError(f"nwalkers must be even and >= 4, got {n}")
+    if nsteps < 0 or burn < 0 or thin < 1 or (swap_every or 0) < 0:
+        raise ValueError(f"nsteps and burn must be >= 0 and thin >= 1, got {nsteps}, {burn}, {thin}" if swap_every is None else
+                         f"nsteps, burn and swap_every must be >= 0 and thin >= 1, got {nsteps}, {burn}, {swap_every}, {thin}")
+
+
+def _draw_starts(seed, shape, start, ball):
+    """The walkers' starts, `shape` = [..., ndim]: ONE uniform draw of that shape from `default_rng(seed)`, mapped into the
+    ball of half-width `ball` around the cube point `start` and clipped to the cube where the two are given."""
+    if (start is None) != (ball is None):
+        raise ValueError("start and ball go together")
+    U = np.random.default_rng(seed).random(shape)
+    if start is not None:
+        centre = np.asarray(start, dtype=float).reshape(shape[-1])
+        U = np.clip(centre + float(ball) * (2.0 * U - 1.0), 0.0, 1.0)
+    return U
+
+
+def _kept_rows(loglike_cube, cube):
+    """The kept cube rows [nkeep, n, ndim] through `loglike_cube` once: their transformed rows [nkeep, n, ...] and, as the
+    keyword for an `EnsembleResult`, lnprior [nkeep, n] where a third array comes back."""
+    nkeep, n, ndim = cube.shape
+    out = loglike_cube(cube.reshape(-1, ndim)) if nkeep else (np.empty((0, n, ndim)),)
+    theta = np.asarray(out[0], dtype=float).reshape(nkeep, n, -1 if nkeep else ndim)
+    return theta, (dict(lnprior=np.asarray(out[2], dtype=float).reshape(nkeep, n)) if len(out) > 2 else {})
+
+
 def ensemble_sample(loglike_cube, advance, ndim, nwalkers, nsteps, burn=0, thin=1, start=None, ball=None, seed=0):
     """`burn` + `nsteps` iterations of `nwalkers` walkers (even, >= 4); see the module's text.  `seed` seeds the host generator
     of the starts and is handed to `advance`."""
     ndim, n, nsteps, burn, thin = int(ndim), int(nwalkers), int(nsteps), int(burn), int(thin)
-    if n < 4 or n % 2:
-        raise ValueError(f"nwalkers must be even and >= 4, got {n}")
-    if nsteps < 0 or burn < 0 or thin < 1:
-        raise ValueError(f"nsteps and burn must be >= 0 and thin >= 1, got {nsteps}, {burn}, {thin}")
-    if (start is None) != (ball is None):
-        raise ValueError("start and ball go together")
-    rng = np.random.default_rng(seed)
-    U = rng.random((n, ndim))
-    if start is not None:
-        centre = np.asarray(start, dtype=float).reshape(ndim)
-        U = np.clip(centre + float(ball) * (2.0 * U - 1.0), 0.0, 1.0)
+    _check_run(n, nsteps, burn, thin)
+    U = _draw_starts(seed, (n, ndim), start, ball)
     if burn:
         U = advance(U, burn, thin=1, seed=seed, first_iter=0, chain=False)[0]
     U, _, _, status, naccept, CU, CL = advance(np.ascontiguousarray(U), nsteps, thin=thin, seed=seed, first_iter=burn, chain=True)
     nkeep = nsteps // thin
     CU, CL = np.asarray(CU, dtype=float).reshape(nkeep, n, ndim), np.asarray(CL, dtype=float).reshape(nkeep, n)
-    out = loglike_cube(CU.reshape(-1, ndim)) if nkeep else (np.empty((0, n, ndim)),)
-    theta = np.asarray(out[0], dtype=float).reshape(nkeep, n, -1 if nkeep else ndim)
-    extra = dict(lnprior=np.asarray(out[2], dtype=float).reshape(nkeep, n)) if len(out) > 2 else {}
+    theta, extra = _kept_rows(loglike_cube, CU)
     return EnsembleResult(cube=CU, theta=theta, logL=CL, **extra, accept_frac=np.asarray(naccept) / max(nsteps, 1), status=np.asarray(status),
                           last=np.asarray(U), nwalkers=n, nsteps=nsteps, burn=burn, thin=thin, seed=seed)

@@ -75,16 +75,20 @@ class TemperedResult:
     def cold(self):
         """The beta[0] rung as an `ensemble.EnsembleResult`; its theta comes from one `loglike_cube` pass over the kept cold
         rows alone.  Its `flat()` goes into `write_equal_weights`, `model_band_batch` and `eqw_batch`."""
-        nkeep, n, ndim = self.cube.shape
-        out = self._loglike_cube(self.cube.reshape(-1, ndim)) if nkeep else (np.empty((0, n, ndim)),)
-        theta = np.asarray(out[0], dtype=float).reshape(nkeep, n, -1 if nkeep else ndim)
-        extra = dict(lnprior=np.asarray(out[2], dtype=float).reshape(nkeep, n)) if len(out) > 2 else {}
+        from .ensemble import _kept_rows                    # (the book-keeping the two drivers share lives in `ensemble`)
+        n = self.cube.shape[1]
+        theta, extra = _kept_rows(self._loglike_cube, self.cube)
         return EnsembleResult(cube=self.cube, theta=theta, **extra, logL=np.ascontiguousarray(self.logL[:, 0, :]), accept_frac=self.naccept[0] / max(self.nsteps, 1),
                               status=self.status[0], last=self.last[0], nwalkers=n, nsteps=self.nsteps, burn=self.burn, thin=self.thin, seed=self.seed)
 
     def _rung(self, t, lo=0, hi=None):
         """The kept logL of rung t over the slots [lo, hi) and the positions of status 0, flattened."""
         return self.logL[lo:hi, t, self.status[t] == 0].reshape(-1)
+
+    def _plus_prior_mass(self, lnZ):
+        """ln Z of the ladder plus ln Z(0): under a Gaussian prior Z(0) is its mass over the cube, a constant; None adds
+        nothing (the value goes through untouched, not as lnZ + 0.0)."""
+        return lnZ if self.ln_prior_mass is None else lnZ + self.ln_prior_mass
 
     def _stepping_stone(self, lo=0, hi=None):
         total = 0.0
@@ -105,9 +109,7 @@ class TemperedResult:
         if nbatch < 2 or size < 1:
             raise ValueError(f"{self.logL.shape[0]} kept iterations cannot be cut into {nbatch} batches")
         parts = np.array([self._stepping_stone(b * size, (b + 1) * size) for b in range(nbatch)])
-        if self.ln_prior_mass is not None:                  # (a Gaussian prior: Z(0) is its mass over the cube, a constant)
-            return self._stepping_stone() + self.ln_prior_mass, float(parts.std(ddof=1) / np.sqrt(nbatch))
-        return self._stepping_stone(), float(parts.std(ddof=1) / np.sqrt(nbatch))
+        return self._plus_prior_mass(self._stepping_stone()), float(parts.std(ddof=1) / np.sqrt(nbatch))
 
     def logZ_ti(self):
         """ln Z by thermodynamic integration: the trapezoid rule over < logL >_beta on the ladder's nodes.  Its bias is the
@@ -115,9 +117,7 @@ class TemperedResult:
         if self.betas[-1] != 0.0:
             raise ValueError(f"thermodynamic integration needs a ladder that ends at beta = 0 (the prior), got {self.betas[-1]}")
         mean = np.array([self._rung(t).mean() for t in range(self.betas.size)])
-        if self.ln_prior_mass is not None:
-            return float((0.5 * (mean[:-1] + mean[1:]) * (self.betas[:-1] - self.betas[1:])).sum()) + self.ln_prior_mass
-        return float((0.5 * (mean[:-1] + mean[1:]) * (self.betas[:-1] - self.betas[1:])).sum())
+        return self._plus_prior_mass(float((0.5 * (mean[:-1] + mean[1:]) * (self.betas[:-1] - self.betas[1:])).sum()))
 
 
 def swap_rounds(first_iter, nsteps, swap_every, ntemps):
@@ -138,19 +138,11 @@ def tempered_sample(loglike_cube, advance, ndim, nwalkers, nsteps, betas, burn=0
     ndim, n, nsteps, burn, thin, swap_every = int(ndim), int(nwalkers), int(nsteps), int(burn), int(thin), int(swap_every)
     betas = np.array(betas, dtype=float).reshape(-1)
     T = betas.size
-    if n < 4 or n % 2:
-        raise ValueError(f"nwalkers must be even and >= 4, got {n}")
-    if nsteps < 0 or burn < 0 or thin < 1 or swap_every < 0:
-        raise ValueError(f"nsteps, burn and swap_every must be >= 0 and thin >= 1, got {nsteps}, {burn}, {swap_every}, {thin}")
+    from .ensemble import _check_run, _draw_starts
+    _check_run(n, nsteps, burn, thin, swap_every)
     if T < 1 or not np.isfinite(betas).all() or (betas < 0.0).any() or (np.diff(betas) >= 0.0).any():
         raise ValueError(f"betas must be finite, >= 0 and strictly decreasing, got {betas}")
-    if (start is None) != (ball is None):
-        raise ValueError("start and ball go together")
-    rng = np.random.default_rng(seed)
-    U = rng.random((T, n, ndim))
-    if start is not None:
-        centre = np.asarray(start, dtype=float).reshape(ndim)
-        U = np.clip(centre + float(ball) * (2.0 * U - 1.0), 0.0, 1.0)
+    U = _draw_starts(seed, (T, n, ndim), start, ball)
     if burn:
         U = advance(U, burn, thin=1, swap_every=swap_every, seed=seed, first_iter=0, chain=False, chain_temps=0)[0]
     U, _, _, status, naccept, nswap, CU, CL = advance(np.ascontiguousarray(U), nsteps, thin=thin, swap_every=swap_every, seed=seed, first_iter=burn,
