@@ -36,7 +36,7 @@ REPORTED = [s for s in DEVICE_SOURCES if s != "grad_kernels.hip"]
 HOST_SOURCES = ["host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp",
                 "host_staged.cpp", "host_grad.cpp", "host_fit.cpp", "host_ns.cpp", "host_ens.cpp", "host_prior.cpp", "host_eqw.cpp", "host_band.cpp", "broker.cpp", "comm.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
-HOST_HEADERS = ["host_ctx.h", "kernel_args.h", "grad_args.h", "eqw_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ens_args.h", "prior_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
+HOST_HEADERS = ["host_ctx.h", "ctx_plan.h", "kernel_args.h", "grad_args.h", "eqw_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ens_args.h", "prior_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
 TARGET = os.path.join(CSRC, "libmcalf_hip.so")
 OBJDIR = os.path.join(CSRC, "obj")
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
@@ -169,9 +169,10 @@ def copy_sources(workdir: str) -> None:
         if f.endswith((".h", ".hip", ".cpp")):
             shutil.copy(os.path.join(CSRC, f), workdir)
     shutil.copy(os.path.join(CSRC, "..", "..", "include", "mcalf_hip.h"), os.path.join(workdir, "include"))
-    hp = os.path.join(workdir, "host_ctx.h")
-    txt = open(hp).read().replace('#include "../../include/mcalf_hip.h"', '#include "include/mcalf_hip.h"')
-    open(hp, "w").write(txt)
+    for name in ("host_ctx.h", "ctx_plan.h"):
+        hp = os.path.join(workdir, name)
+        txt = open(hp).read().replace('#include "../../include/mcalf_hip.h"', '#include "include/mcalf_hip.h"')
+        open(hp, "w").write(txt)
 
 
 def resource_table(log: str, only: str = "fused"):

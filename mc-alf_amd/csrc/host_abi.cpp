@@ -94,226 +94,50 @@ extern "C" void mcalf_destroy(mcalf_ctx* ctx) {
 }
 
 static int create_impl(const mcalf_spec* sp, mcalf_ctx* ctx) {
-    if (!sp) return set_err(ctx, MCALF_ERR_INVALID, "spec is NULL");
-    if (sp->npix <= 0 || !sp->wl || !sp->flux || !sp->err)
-        return set_err(ctx, MCALF_ERR_INVALID, "npix must be > 0 and wl/flux/err non-NULL");
-    if (sp->npix > (1 << 30)) return set_err(ctx, MCALF_ERR_RANGE, "npix too large");
-    if (sp->nlines <= 0 || !sp->lines) return set_err(ctx, MCALF_ERR_INVALID, "need at least one line");
-    if (sp->ncompmax < 0 || sp->nfill < 0) return set_err(ctx, MCALF_ERR_INVALID, "negative component counts");
-    if (!(sp->velstep > 0.0)) return set_err(ctx, MCALF_ERR_INVALID, "velstep must be > 0");
-    if (sp->conv_mode != MCALF_CONV_WRAP_NUMPY && sp->conv_mode != MCALF_CONV_SAME_EDGE_JAX)
-        return set_err(ctx, MCALF_ERR_INVALID, "unknown conv_mode %d", sp->conv_mode);
-    double rmax = sp->specres_max;
-    if (!sp->freespecres && !(rmax >= sp->specres_fixed)) rmax = sp->specres_fixed;
-    if (!(rmax > 0.0) || !std::isfinite(rmax))
-        return set_err(ctx, MCALF_ERR_INVALID, "specres_max must be finite and > 0");
-
-    int rc = pick_device(ctx, sp->device, &ctx->device, &ctx->arch);
-    if (rc) return rc;
+    // check, pick the device, plan (ctx_plan.h: everything the spec decides), upload
+    std::string why;
+    int rc = check_spec(sp, &why);
+    if (rc) return set_err(ctx, rc, "%s", why.c_str());
+    if ((rc = pick_device(ctx, sp->device, &ctx->device, &ctx->arch))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CtxShape& shape = *ctx;
+    CtxTables tab;
+    if ((rc = plan_shape(*sp, ctx->env.lines_per_sync, &shape, &why))) return set_err(ctx, rc, "%s", why.c_str());
+    plan_tables(*sp, &shape, &tab);
 
-    ctx->npix = sp->npix;
-    ctx->nlines = sp->nlines;
-    ctx->ncompmax = sp->ncompmax;
-    ctx->nfill = sp->nfill;
-    ctx->freespecres = sp->freespecres ? 1 : 0;
-    ctx->freecont = sp->freecont ? 1 : 0;
-    ctx->conv_mode = sp->conv_mode;
-    ctx->specres_fixed = sp->specres_fixed;
-    ctx->specres_max = rmax;
-    ctx->contval_fixed = sp->contval_fixed;
-    ctx->velstep = sp->velstep;
-    ctx->asymm = sp->asymmlike ? 1 : 0;                                  // hires_fitter.py:296-303
-    ctx->veto4 = sp->asymm_n4 + 0.01 * (double)sp->npix;                 // gauss_cdf[1] + gracenum (:181,302)
-    ctx->veto5 = sp->asymm_n5 + 0.01 * (double)sp->npix;                 // gauss_cdf[2] + gracenum (:300)
-    ctx->startind = ctx->freecont + ctx->freespecres;             // hires_fitter.py:169-174
-    ctx->endind = ctx->startind + 3 * ctx->ncompmax + 1;          // :176
-    ctx->ndim = ctx->endind + 3 * ctx->nfill;                     // :184-200
-
-    // LSF reach and tiling
-    const double sigma_max = (rmax / kFwhmToSigma) / sp->velstep;
-    if (ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX) {
-        ctx->jax_half = (int)std::ceil((float)(kKernelReach * sigma_max));   // :557-559 (float32 ceil)
-        ctx->n_cap = ctx->jax_half;
-        if (2L * ctx->jax_half + 1 > ctx->npix)
-            return set_err(ctx, MCALF_ERR_INVALID,
-                           "JAX-path LSF kernel (%d taps) is longer than the spectrum (%ld px): the reference's "
-                           "jnp.convolve(..., 'same') / jnp.where (hires_fitter.py:674-681) cannot broadcast either",
-                           2 * ctx->jax_half + 1, ctx->npix);
-    } else {
-        ctx->n_cap = (rmax > sp->velstep) ? (int)std::ceil(kKernelReach * sigma_max) : 0;
-    }
-    ctx->ncl_cap = std::max(1, ctx->ncompmax * ctx->nlines + ctx->nfill);
-    // Lines per barrier: 5 when that saves a barrier at the context's largest line count and the extra folded
-    // tables cost no tile pixels (LDS), else 4.
-    auto fixed_for = [&](int lps) {
-        return 2 * (size_t)lps * kTabPad + (size_t)ctx->ncl_cap * kRecStride + (2 * (size_t)ctx->n_cap + 8) + kRedDoubles +
-               64 * VT_INODES;
-    };
-    auto ext_for = [&](int lps) {
-        size_t e = kExtMax;
-        while (e > 0 && (fixed_for(lps) + tile_doubles((int)e)) * sizeof(double) > kLdsBudget) e -= 64;
-        return e;
-    };
-    ctx->lps = ((ctx->ncl_cap + 4) / 5 < (ctx->ncl_cap + 3) / 4 && ext_for(5) == ext_for(4)) ? 5 : 4;
-    if (ctx->env.lines_per_sync == 4 || (ctx->env.lines_per_sync == 5 && ext_for(5) == ext_for(4))) ctx->lps = ctx->env.lines_per_sync;
-    if (ext_for(ctx->lps) < 2 * (size_t)ctx->n_cap + 64) {
-        // The LSF does not fit a workgroup tile with its halo: the fused kernel then runs without convolution (a tile
-        // without halo) and the wide kernels convolve behind it (launch_wide) -- the reference simply builds a longer
-        // kernel (hires_fitter.py:458-464; JAX semantics: its fixed grid, :549-560, whatever its length).
-        if (2.0 * (double)ctx->n_cap + 1.0 > 6.0e7)
-            return set_err(ctx, MCALF_ERR_RANGE,
-                           "LSF half-width %d px (specres_max %.3g km/s at %.3g km/s/px) with %d component-lines does not "
-                           "fit a %d-pixel workgroup tile / the %zu-byte LDS budget", ctx->n_cap, rmax, sp->velstep,
-                           ctx->ncl_cap, kExtMax, kLdsBudget);
-        ctx->wide = 1;
-        ctx->wide_n_cap = ctx->n_cap;
-        ctx->n_cap = 0;
-        ctx->lps = ((ctx->ncl_cap + 4) / 5 < (ctx->ncl_cap + 3) / 4 && ext_for(5) == ext_for(4)) ? 5 : 4;
-    }
-    const size_t fixed_doubles = fixed_for(ctx->lps);
-    size_t ext = ext_for(ctx->lps);
-    if (ext < 2 * (size_t)ctx->n_cap + 64)
-        return set_err(ctx, MCALF_ERR_RANGE, "%d component-lines do not fit the %zu-byte LDS budget", ctx->ncl_cap, kLdsBudget);
-    // tiles are multiples of 8 pixels (the epilogue works in aligned groups of 8), balanced over the spectrum
-    const long tmax = ((long)ext - 2 * ctx->n_cap) & ~7L;
-    long tile = std::min(tmax, (ctx->npix + 7) & ~7L);
-    long ntiles = (ctx->npix + tile - 1) / tile;
-    tile = (((ctx->npix + ntiles - 1) / ntiles) + 7) & ~7L;
-    ntiles = (ctx->npix + tile - 1) / tile;
-    ctx->tile = (int)tile;
-    ctx->ntiles = (int)ntiles;
-    ctx->lds_bytes = (fixed_doubles + (size_t)tile_doubles((int)tile + 2 * ctx->n_cap)) * sizeof(double);
-    ctx->lds_bytes_inline = (fixed_for(4) + (size_t)tile_doubles((int)tile + 2 * ctx->n_cap)) * sizeof(double);
-    ctx->selfhalo = (ntiles == 1 && ctx->n_cap < ctx->npix) ? 1 : 0;
-
-    // spectrum arrays (float64 host arithmetic identical to the reference's numpy expressions)
-    // Self-halo contexts index nu by thread (0 .. kExtMax-1): the entries past the spectrum are VIRTUAL pixels.
-    // Up to the next multiple of 64 they continue the wavelength grid when it is recognisably linear or
-    // logarithmic over its last 64 pixels (so that the last, partial segment can be interpolated like the
-    // others; the virtual pixels' own results are never stored); beyond that they repeat the last value.
-    const long nu_len = ctx->selfhalo ? (long)kExtMax : ctx->npix;
-    std::vector<double> nu(nu_len), is2(ctx->npix), lg(ctx->npix);
-    for (long i = 0; i < ctx->npix; ++i) {
-        const double wave_cm = sp->wl[i] / 1e8;            // :376
-        nu[i] = kCcgs / wave_cm;                           // :362 at zp1 = 1
-        is2[i] = 1.0 / (sp->err[i] * sp->err[i]);          // :292
-        lg[i] = std::log(is2[i]);                          // :294
-    }
-    if (ctx->selfhalo) {
-        const long n = ctx->npix, upto = std::min<long>(nu_len, (n + 63) & ~63L);
-        int kind = 0;                                      // 1 linear, 2 logarithmic
-        if (n >= 66) {
-            const double d = sp->wl[n - 1] - sp->wl[n - 2], r = sp->wl[n - 1] / sp->wl[n - 2];
-            bool lin = true, lg_ = true;
-            for (long i = n - 64; i < n - 1; ++i) {
-                if (!(std::fabs((sp->wl[i + 1] - sp->wl[i]) - d) <= 1e-9 * std::fabs(d))) lin = false;
-                if (!(std::fabs(sp->wl[i + 1] / sp->wl[i] - r) <= 1e-9 * std::fabs(r - 1.0))) lg_ = false;
-            }
-            kind = lin ? 1 : (lg_ ? 2 : 0);
-        }
-        // the common step from the pixels 64 apart (averages the grid's own rounding noise)
-        const double step = kind == 1 ? (sp->wl[n - 1] - sp->wl[n - 65]) / 64.0
-                          : kind == 2 ? std::exp(std::log(sp->wl[n - 1] / sp->wl[n - 65]) / 64.0) : 0.0;
-        for (long i = n; i < nu_len; ++i) {
-            if (kind != 0 && i < upto) {
-                const double m = (double)(i - (n - 1));
-                const double wl = kind == 1 ? sp->wl[n - 1] + m * step : sp->wl[n - 1] * std::pow(step, m);
-                nu[i] = kCcgs / (wl / 1e8);
-            } else {
-                // past the last (partial) segment nothing is ever stored: nu = 0 puts these lanes at u = -nu0/dnu,
-                // thousands of Doppler widths away from every line, so their segments go the cheap node-only way
-                nu[i] = (i >= upto) ? 0.0 : nu[i - 1];
-            }
-        }
-    }
-    std::vector<LineDev> lines(ctx->nlines + 1);
-    for (int l = 0; l <= ctx->nlines; ++l) {
-        const mcalf_line& src = (l < ctx->nlines) ? sp->lines[l] : sp->fill;
-        lines[l].wrest_cm = src.wrest_A / 1e8;             // :376
-        lines[l].f = src.f;
-        lines[l].gamma4pi = src.gamma / (4.0 * M_PI);      // :361
-        lines[l].nujk = kCcgs / lines[l].wrest_cm;         // :359
-    }
     const size_t nb = (size_t)ctx->npix * sizeof(double);
     const size_t nbp = nb + 8 * sizeof(double);          // the epilogue reads 8 pixels per thread without a bounds test
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_nu.p, (size_t)nu_len * sizeof(double)));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_nu.p, tab.nu.size() * sizeof(double)));
     for (DevBuf<double>* b : {&ctx->d_obj, &ctx->d_ispec2, &ctx->d_lgis, &ctx->d_err}) {
         HIP_TRY(ctx, hipMalloc((void**)&b->p, nbp));
         HIP_TRY(ctx, hipMemset(b->p, 0, nbp));
     }
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_lines.p, lines.size() * sizeof(LineDev)));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_nu, nu.data(), (size_t)nu_len * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_lines.p, tab.lines.size() * sizeof(LineDev)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_nu, tab.nu.data(), tab.nu.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_obj, sp->flux, nb, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_ispec2, is2.data(), nb, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_lgis, lg.data(), nb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_ispec2, tab.ispec2.data(), nb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_lgis, tab.lgis.data(), nb, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_err, sp->err, nb, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_lines, lines.data(), lines.size() * sizeof(LineDev), hipMemcpyHostToDevice));
-    rc = upload_tables(ctx, &ctx->d_tabs.p);
-    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->d_lines, tab.lines.data(), tab.lines.size() * sizeof(LineDev), hipMemcpyHostToDevice));
+    if ((rc = upload_tables(ctx, &ctx->d_tabs.p))) return rc;
     if ((rc = eqw_prepare(ctx, sp->wl))) return rc;
-
-    // Far-wing interpolation set-up: which 64-pixel segments of each tile may be interpolated in
-    // pixel-index space.  A segment qualifies when it lies inside the tile's extent without crossing
-    // the periodic seam and nu(pixel) itself is reproduced by the 8-node interpolant to 1e-15 (true
-    // for linear / logarithmic wavelength grids, false across masked gaps).
-    std::vector<unsigned long long> segok(ctx->ntiles, 0ULL);
-    double dnu_seg = 0.0;
-    for (int t = 0; t < ctx->ntiles; ++t) {
-        const long t0 = (long)t * ctx->tile;
-        const long tlen = std::min<long>(ctx->tile, ctx->npix - t0);
-        const long ext0 = ctx->selfhalo ? 0 : t0 - ctx->n_cap, extCount = tlen + 2L * ctx->n_cap;
-        for (int m = 0; m < 64; ++m) {
-            const long i0 = 64L * m;
-            const long e0 = ext0 + i0;
-            if (ctx->selfhalo) {
-                if (e0 + 63 >= nu_len) continue;
-                if (e0 >= ((ctx->npix + 63) & ~63L)) {          // wholly virtual (nu = 0): nothing to get wrong
-                    segok[t] |= 1ULL << m;
-                    continue;
-                }
-                // otherwise: real pixels, the last segment completed by the virtual continuation of the grid
-            } else {
-                if (i0 + 64 > extCount) continue;
-                if (e0 < 0 || e0 + 63 >= ctx->npix) continue;
-            }
-            bool ok = true;
-            const double dir = nu[e0 + 63] - nu[e0];
-            for (int i = 0; i < 64 && ok; ++i) {
-                double v = 0.0;
-                for (int k = 0; k < VT_INODES; ++k) v += VT_INTERP_W_HOST[i * VT_INODES + k] * nu[e0 + VT_INTERP_NODES[k]];
-                const double x = nu[e0 + i];
-                if (!std::isfinite(x) || !(std::fabs(v - x) <= 1e-15 * std::fabs(x))) ok = false;
-                if (i > 0 && !((nu[e0 + i] - nu[e0 + i - 1]) * dir > 0.0)) ok = false;   // strictly monotonic
-            }
-            if (!ok) continue;
-            segok[t] |= 1ULL << m;
-            dnu_seg = std::max(dnu_seg, std::fabs(dir));
-        }
-    }
-    ctx->dnu_seg = dnu_seg;
-    // The set-up finds a record's segment-mask word by boundary search where the ends of the tile's real segments form a
-    // monotone sequence (established here, once; a wavelength array out of order keeps the walk over all 64 segments).
-    ctx->seg_search = (ctx->selfhalo && seg_ends_searchable(nu.data(), ctx->npix, &ctx->seg_nreal)) ? 1 : 0;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_segok.p, segok.size() * sizeof(unsigned long long)));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_segok, segok.data(), segok.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_segok.p, tab.segok.size() * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_segok, tab.segok.data(), tab.segok.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_wtab.p, sizeof(VT_INTERP_W_HOST)));
     HIP_TRY(ctx, hipMemcpy(ctx->d_wtab, VT_INTERP_W_HOST, sizeof(VT_INTERP_W_HOST), hipMemcpyHostToDevice));
     // more than 64 KiB of dynamic LDS needs the attribute (2 workgroups x 78 KiB fit the 160 KiB of a CU)
     for (int k = 0; k < fused_kernel_count(); ++k)
         HIP_TRY(ctx, hipFuncSetAttribute(fused_kernel_at(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
     if ((rc = create_stream(ctx, &ctx->stream))) return rc;
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        if ((rc = stream_probe_xcds(ctx))) return rc;         // (the streaming launch is for one device shape only)
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_queue.p, kMaxChunks * sizeof(unsigned int)));
-        HIP_TRY(ctx, hipMemset(ctx->d_queue, 0, kMaxChunks * sizeof(unsigned int)));
-        // (the environment's snapshot was applied at the top of mcalf_create; what depends on the device is finished here)
-        ctx->inline_max_items = ctx->env.inline_max >= 0 ? ctx->env.inline_max : 2 * ctx->num_cu;   // launches that fit the chip in one round of workgroups
-        if (ctx->env.stream_wgs >= 0) ctx->stream_wgs = std::min(ctx->env.stream_wgs, ctx->num_cu);
-    }
+    hipDeviceProp_t prop;
+    HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
+    ctx->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if ((rc = stream_probe_xcds(ctx))) return rc;         // (the streaming launch is for one device shape only)
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_queue.p, kMaxChunks * sizeof(unsigned int)));
+    HIP_TRY(ctx, hipMemset(ctx->d_queue, 0, kMaxChunks * sizeof(unsigned int)));
+    // (the environment's snapshot was applied at the top of mcalf_create; what depends on the device is finished here)
+    ctx->inline_max_items = ctx->env.inline_max >= 0 ? ctx->env.inline_max : 2 * ctx->num_cu;   // launches that fit the chip in one round of workgroups
+    if (ctx->env.stream_wgs >= 0) ctx->stream_wgs = std::min(ctx->env.stream_wgs, ctx->num_cu);
     return MCALF_OK;
 }
 

@@ -1,6 +1,8 @@
 // Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
-// Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.
+// Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.  What a context
+// decides from its spec alone -- the checks, the launch geometry, the host tables -- is ctx_plan.h (no HIP there: the CPU tests
+// plan with it); mcalf_ctx inherits the planned scalars (CtxShape) and adds what belongs to a device.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>   // types only: the library is resolved at run time (mcalf_comm_*), never linked
@@ -24,6 +26,7 @@
 #include "../../include/mcalf_hip.h"
 #pragma GCC visibility pop
 #include "kernel_args.h"
+#include "ctx_plan.h"
 #include "grad_args.h"
 #include "prior_args.h"
 
@@ -153,7 +156,7 @@ struct DevBuf {
 };
 template <typename T> using PinBuf = DevBuf<T, true>;
 
-struct mcalf_ctx {
+struct mcalf_ctx : CtxShape {               // (the problem and geometry fields: ctx_plan.h)
     HostTrace htrace;
     BlockTimeline btrace;
     StreamTrace strace;
@@ -161,23 +164,11 @@ struct mcalf_ctx {
     int device = 0;
     std::string arch;
     std::string err;
-    // problem
-    long npix = 0;
-    int nlines = 0, ncompmax = 0, nfill = 0, freespecres = 0, freecont = 0, conv_mode = 0;
-    int ndim = 0, startind = 0, endind = 0;
-    double specres_fixed = 0, specres_max = 0, contval_fixed = 1, velstep = 0;
-    int asymm = 0;
-    double veto4 = 0, veto5 = 0;
-    // geometry
-    int n_cap = 0, tile = 0, ntiles = 0, ncl_cap = 0, jax_half = 0, selfhalo = 0, lps = 4;
-    size_t lds_bytes = 0, lds_bytes_inline = 0;    // (the one-launch variant of small calls folds 4 lines per barrier)
     int inline_max_items = 0;                      // launches of at most this many work items take the one-launch variant
     // device buffers
     DevBuf<double> d_nu, d_obj, d_ispec2, d_lgis, d_err, d_tabs, d_wtab;
     DevBuf<LineDev> d_lines;
     DevBuf<unsigned long long> d_segok;
-    double dnu_seg = 0;
-    int seg_nreal = 0, seg_search = 0;  // single-tile contexts: real segments, and whether the set-up may search their ends (kernel_args.h)
     // workspaces (grown on demand)
     DevBuf<double> d_P, d_out, d_partial, d_model, d_bounds, d_prior, d_recs, d_taps;
     DevBuf<SampleHdr> d_hdr;
@@ -276,8 +267,7 @@ struct mcalf_ctx {
     double stream_timeout_s = 0.5;          // MCALF_STREAM_TIMEOUT: longest wait of a wave inside the kernel
     // LSF wider than a workgroup tile (numpy boundary): the fused kernel runs WITHOUT convolution and continuum into
     // d_wide, two more kernels do taps, periodic convolution, continuum and terms from HBM (host_wide.cpp: launch_wide).
-    // n_cap is 0 for such a context (the tile carries no halo); wide_n_cap is the half-width provisioned from specres_max.
-    int wide = 0, wide_n_cap = 0;
+    // Whether a context is one, and the half-width it provisions, are CtxShape's wide and wide_n_cap.
     DevBuf<double> d_wide, d_wtaps, d_wpartial, d_wrows;
     DevBuf<SampleHdr> d_whdr;
     mcalf_launch_info_t last = {};      // what the last call did (mcalf_last_launch)
@@ -332,7 +322,7 @@ struct mcalf_ctx {
     DevBuf<double> ens_pr;                  // lnprior of the walkers [T n], grown by a call under a Gaussian prior only
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
-    // fields are copies of sub-context 0's, for mcalf_info).
+    // fields, its CtxShape, are a copy of sub-context 0's, for mcalf_info).
     std::vector<mcalf_ctx*> subs;
     struct MultiPool* pool = nullptr;
     int multi_last_active = 0;              // sub-contexts the last call was cut over

@@ -83,13 +83,7 @@ extern "C" int mcalf_create_multi(const mcalf_spec* spec, const int32_t* devices
     const mcalf_ctx* s0 = ctx->subs[0];
     ctx->env = s0->env;
     ctx->device = s0->device; ctx->arch = s0->arch;
-    ctx->npix = s0->npix; ctx->nlines = s0->nlines; ctx->ncompmax = s0->ncompmax; ctx->nfill = s0->nfill;
-    ctx->freespecres = s0->freespecres; ctx->freecont = s0->freecont; ctx->conv_mode = s0->conv_mode;
-    ctx->ndim = s0->ndim; ctx->startind = s0->startind; ctx->endind = s0->endind;
-    ctx->specres_fixed = s0->specres_fixed; ctx->specres_max = s0->specres_max; ctx->contval_fixed = s0->contval_fixed;
-    ctx->velstep = s0->velstep; ctx->asymm = s0->asymm; ctx->veto4 = s0->veto4; ctx->veto5 = s0->veto5;
-    ctx->n_cap = s0->n_cap; ctx->tile = s0->tile; ctx->ntiles = s0->ntiles; ctx->ncl_cap = s0->ncl_cap; ctx->jax_half = s0->jax_half;
-    ctx->selfhalo = s0->selfhalo; ctx->lps = s0->lps; ctx->wide = s0->wide; ctx->wide_n_cap = s0->wide_n_cap;
+    static_cast<CtxShape&>(*ctx) = *s0;
     ctx->num_cu = s0->num_cu; ctx->xcd_mask = s0->xcd_mask; ctx->ns_compact = s0->ns_compact;
     ctx->pool = new (std::nothrow) MultiPool();
     if (!ctx->pool) { multi_release(ctx); delete ctx; return set_err(nullptr, MCALF_ERR_NOMEM, "out of host memory"); }

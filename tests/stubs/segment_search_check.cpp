@@ -1,6 +1,6 @@
 // tests/test_segment_search_host.py: the segment-mask words by boundary search against the walk over every segment, word for
 // word, both from mc-alf_amd/csrc/kernel_args.h (the source the set-up kernel compiles), and the precondition function
-// mcalf_create decides with.  Built with -ffp-contract=off; prints one line per grid and "FAIL ..." lines, exits 1 on any.
+// mcalf_create decides with; the grids' pixel frequencies are laid out by mcalf_create's own fill_nu (ctx_plan.h).  Built with -ffp-contract=off; prints one line per grid and "FAIL ..." lines, exits 1 on any.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -11,30 +11,33 @@
 #include <random>
 #include <vector>
 
+#include "ctx_plan.h"
 #include "kernel_args.h"
 
 using namespace mcalf;
 
-static const double kC = 2.9979245e10, kInf = std::numeric_limits<double>::infinity(), kNaN = std::numeric_limits<double>::quiet_NaN();
+static const double kInf =std::numeric_limits<double>::infinity(), kNaN = std::numeric_limits<double>::quiet_NaN();
 
 struct Grid {
     const char* name;
-    std::vector<double> nu;      // 4096 entries, as mcalf_create lays them out for a single-tile context
+    std::vector<double> nu;      // 4096 entries, laid out by mcalf_create's fill_nu for a single-tile context
     long npix;
     uint64_t ok;                 // interpolable segments (bit m = segment m)
 };
 
-// A logarithmic grid of 2 km/s pixels from 6190 A (`dir` < 0: descending wavelengths), continued virtually up to the next
-// multiple of 64 pixels, nu = 0 beyond; with `seam` the wavelengths jump by 30 pixels after pixel 299.
+// A logarithmic grid of 2 km/s pixels from 6190 A (`dir` < 0: descending wavelengths), which fill_nu continues virtually up to
+// the next multiple of 64 pixels (from 66 pixels on: a shorter grid repeats its last value), nu = 0 beyond; with `seam` the
+// wavelengths jump by 30 pixels after pixel 299.
 static Grid make_grid(const char* name, long npix, int dir = 1, bool seam = false, bool repeat_tail = false) {
     Grid g{name, std::vector<double>(4096, 0.0), npix, 0};
     const long upto = (npix + 63) & ~63L;
-    for (long i = 0; i < upto; ++i) {
+    std::vector<double> wl(npix);
+    for (long i = 0; i < npix; ++i) {
         const long k = (seam && i >= 300) ? i + 30 : i;
-        const double wl = 6190.0 * std::exp((double)(dir * k) * 2.0 / 2.99792458e5);
-        g.nu[i] = kC / (wl / 1e8);
-        if (repeat_tail && i >= npix) g.nu[i] = g.nu[i - 1];         // a grid create does not recognise: the last value repeated
+        wl[i] = 6190.0 * std::exp((double)(dir * k) * 2.0 / 2.99792458e5);
     }
+    fill_nu(wl.data(), npix, (long)g.nu.size(), g.nu.data());
+    for (long i = npix; repeat_tail && i < upto; ++i) g.nu[i] = g.nu[i - 1];      // a grid create does not recognise: the last value repeated
     for (int m = 0; m < 64; ++m) {
         bool ok = true;
         if (64L * m < upto) {

@@ -40,7 +40,7 @@ sys.path.insert(0, root)
 import importlib  # noqa: E402
 bld = importlib.import_module("mc-alf_amd.build")
 bld.copy_sources(work)
-FILES = ["kernels.hip", "kernel_args.h", "host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp"]
+FILES = ["kernels.hip", "kernel_args.h", "ctx_plan.h", "host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp"]
 text = {f: open(os.path.join(work, f)).read() for f in FILES}
 
 

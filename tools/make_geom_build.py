@@ -30,7 +30,7 @@ sys.path.insert(0, root)
 import importlib  # noqa: E402
 bld = importlib.import_module("mc-alf_amd.build")
 bld.copy_sources(work)
-FILES = ["kernels.hip", "kernel_args.h", "host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp"]
+FILES = ["kernels.hip", "kernel_args.h", "ctx_plan.h", "host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp"]
 text = {f: open(os.path.join(work, f)).read() for f in FILES}
 
 
@@ -83,7 +83,7 @@ rep("""            for (int jj = 0; jj < 2; ++jj) {
 rep("            if (r >= a.nrows) continue;\n", "            if (r >= a.nrows || wave >= 8) continue;\n")
 rep("        if (lane < cnt) {\n            const int r = stream_row(x, 8 * (c + lane) + wave, nx);\n            if (r < a.nrows)",
     "        if (lane < cnt && wave < 8) {\n            const int r = stream_row(x, 8 * (c + lane) + wave, nx);\n            if (r < a.nrows)")
-rep("    const long nu_len = ctx->selfhalo ? (long)kExtMax : ctx->npix;", "    const long nu_len = ctx->selfhalo ? (long)kThreadPix : ctx->npix;")
+rep("    t->nu.assign(s.selfhalo ? (size_t)kExtMax : (size_t)s.npix, 0.0);", "    t->nu.assign(s.selfhalo ? (size_t)kThreadPix : (size_t)s.npix, 0.0);")
 if args.cf_lds:
     rep("""    double cF[VT_FDEG + 1];
 #pragma unroll
