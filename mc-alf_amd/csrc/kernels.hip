@@ -791,7 +791,7 @@ __device__ __forceinline__ void stream_exit(const KArgs& a, int tid) {
 struct ItemLoads {
     double treg[(VT_NY * VT_NTOT + kBlock - 1) / kBlock];   // this thread's slice of the universal table T
     double rreg[2];                                         // its slice of the sample's records (covers ncl_cap <= 128)
-    double tapreg;                                          // its LSF tap
+    double tapreg;                                          // its LSF tap (batch instantiations: unused, the taps are scalar operands)
     double nu[kPpt];                                        // pixel frequencies of the tile
     double nuNode;                                          // this lane's interpolation node
     unsigned long long tileMask;                            // interpolable segments of the tile
@@ -808,6 +808,10 @@ constexpr unsigned long long interp_node_word() {
 constexpr unsigned long long kNodeWord = interp_node_word();
 static_assert(VT_INODES == 8 && kNodeWord == 0x3F3C3327180C0300ULL, "node offsets 0, 3, 12, 24, 39, 51, 60, 63: one byte each");
 __device__ __forceinline__ int interp_node(int k) { return (int)((kNodeWord >> (8 * (k & 7))) & 0xFFu); }
+
+// Eight LSF taps, read through the constant address space with a wave-uniform address: one scalar load of sixteen dwords.
+typedef double TapGroupV __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) const TapGroupV __attribute__((aligned(8))) TapGroup;
 
 // Issue every global load of work item w: no load's address depends on another load's answer, and nothing here reads
 // a loaded value, so no wait sits between the first load and the last -- they are drained in one place, at the top of the
@@ -838,7 +842,7 @@ __device__ __forceinline__ void request_item(const KArgs& a, int w, int tid, Ite
         L.hd = kCoh ? *reinterpret_cast<const SampleHdr*>(reinterpret_cast<const double*>(a.hdr) + (size_t)s * a.hdr_stride) : a.hdr[s];
 #pragma unroll
         for (int i = 0; i < kRecRegs; ++i) L.rreg[i] = gr[min(tid + i * kBlock, recTotal - 1)];   // (as the T slices: no test)
-        L.tapreg = gt[min(tid, tapTotal - 1)];
+        if (kCoh) L.tapreg = gt[min(tid, tapTotal - 1)];    // (batch launches read the tap row with scalar loads: fused_items, 3+4)
     }
     const int t0 = tileIdx * a.tile;
     const int ext0 = selfHalo ? 0 : t0 - a.n_cap;
@@ -904,6 +908,10 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
     constexpr bool selfHalo = kSelfHalo;               // (a.selfhalo chooses the instantiation on the host)
     // the records carry segment-mask words (setup_sample(..., segMasks)) and the nodes sit on adjacent segments: eval_line<true>
     constexpr bool kPreMask = kSelfHalo && !kInline;
+    // batch launches read the LSF taps as scalar operands, straight from the set-up kernel's rows.  (The one-launch variant
+    // has no row in memory -- wave 0 writes the taps into sW; a streaming launch reads rows that workgroups of the SAME
+    // launch have just written, which the scalar data cache does not see: both read the taps from sW.)
+    constexpr bool kTapsScalar = !kInline && !kStream;
     static_assert(kLinesPerSync * kTabPad >= kBlock, "the node sums fit the idle half of the folded tables");
     if (kFarInterp) sWt[(tid0 & 7) * 64 + (tid0 >> 3)] = a.wtab[tid0];      // kBlock == 64 * VT_INODES
     const int recTotal = a.ncl_cap * kRecStride, tapTotal = 2 * a.n_cap + 8;
@@ -1013,8 +1021,8 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
                 const double* gr = a.recs + (size_t)s * (kStream ? a.rec_stride : recTotal);
                 for (int i = tid + kRecRegs * kBlock; i < recTotal; i += kBlock) sRec[i] = gr[i];
             }
-            if (tid < tapTotal) sW[tid] = L.tapreg;
-            if (tapTotal > kBlock) {
+            if (kStream && tid < tapTotal) sW[tid] = L.tapreg;
+            if (kStream && tapTotal > kBlock) {
                 const double* gt = a.taps + (kStream ? (size_t)s * a.tap_stride : (a.taps_shared ? 0 : (size_t)s * tapTotal));
                 for (int i = tid + kBlock; i < tapTotal; i += kBlock) sW[i] = gt[i];
             }
@@ -1244,10 +1252,69 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
             for (int m = 0; m < 8; ++m) { ob[m] = a.obj[o0 + m]; is2[m] = a.ispec2[o0 + m]; lg[m] = a.lgis[o0 + m]; }
             double win[8], top[8];
             const double* fp = sF + tid;                   // element 8 tid + 8 c + r  ->  fp[r * kPlaneStride + c]
+            const int ntaps = 2 * n + 1;
+            if constexpr (kTapsScalar) {
+                // The weights are the same in every lane and every wave, and the set-up kernel has left the live point's
+                // row in memory: a group of eight comes as ONE scalar load (sixteen dwords) and every FMA takes its weight
+                // as the scalar operand.  Two register sets take turns, each group issuing the load of the one behind it,
+                // so no weight is ever moved; the row holds 2 n_cap + 8 doubles and 2 n + 1 is odd, so the group behind a
+                // whole one -- at least the remainder's -- always lies inside the row.
+                const int su = __builtin_amdgcn_readfirstlane(s);
+                const TapGroup* gw = (const TapGroup*)(a.taps + (a.taps_shared ? (size_t)0 : (size_t)su * tapTotal));
+                TapGroupV wA = gw[0], wB;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) { win[m] = fp[m * kPlaneStride]; top[m] = 0.0; }
+                auto whole = [&](const TapGroupV& wg) {
+                    ++fp;
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+#pragma unroll
+                        for (int m = 0; m < 8; ++m) top[m] = fma(win[(m + r) & 7], wg[r], top[m]);
+                        win[r] = fp[r * kPlaneStride];     // element base + q0 + r + 8
+                    }
+                    // (a group's reads stay its own: issued among the FMAs of the group before, or merged with the next
+                    // group's into two-address reads, they held a second window of sixteen registers, which the kernel
+                    // does not have -- one to five spills.  Inside the group the scheduler is free: it sends the reads out
+                    // four at a time, into the registers of the values they replace)
+                    __builtin_amdgcn_sched_barrier(0);
+                    asm volatile("" ::: "memory");
+                };
+                auto last = [&](const TapGroupV& wg) {         // the last 1..7 taps (2n+1 is odd): no zero-weight padding taps
+                    const int rem = ntaps & 7;                 // wave-uniform
+                    ++fp;
+#pragma unroll
+                    for (int r = 0; r < 7; ++r) {
+                        if (r >= rem) break;
+#pragma unroll
+                        for (int m = 0; m < 8; ++m) top[m] = fma(win[(m + r) & 7], wg[r], top[m]);
+                        win[r] = fp[r * kPlaneStride];
+                    }
+                };
+                int groups = ntaps >> 3;                       // whole groups of eight taps
+                // (the first group's weights are waited for HERE, with the window: left to the loop, the wait stands at the loop's
+                // top, behind the load of the next group, and is taken on every trip -- scalar loads are counted out of order)
+                asm volatile("" : : "s"(wA[0]));
+                // (ONE exit, at the loop's top, and one copy of the remainder behind it: with a second exit between the halves,
+                // with the odd group peeled off ahead of the loop or behind it, or with a remainder per register set, the
+                // window and the sums were copied where the paths meet, or spilled: up to 77 registers to scratch)
+                bool inB = false;                              // the remainder's weights: which set holds them
+                for (; groups > 0; groups -= 2) {
+                    wB = *++gw;
+                    __builtin_amdgcn_sched_barrier(0);         // (the load goes out at the group's top, ahead of its reads)
+                    whole(wA);
+                    if (groups > 1) {
+                        wA = *++gw;
+                        __builtin_amdgcn_sched_barrier(0);
+                        whole(wB);
+                    } else {
+                        inB = true;
+                    }
+                }
+                last(inB ? wB : wA);
+            } else {
 #pragma unroll
             for (int m = 0; m < 8; ++m) { win[m] = fp[m * kPlaneStride]; top[m] = 0.0; }
             const double* wp = sW;
-            const int ntaps = 2 * n + 1;
             for (int q0 = 0; q0 + 8 <= ntaps; q0 += 8) {   // whole groups of eight taps
                 ++fp;
 #pragma unroll
@@ -1270,6 +1337,7 @@ __device__ __forceinline__ void fused_items(const KArgs& a, double* smem) {
                     for (int m = 0; m < 8; ++m) top[m] = fma(win[(m + r) & 7], wgt, top[m]);
                     win[r] = fp[r * kPlaneStride];
                 }
+            }
             }
             const double ibot = 1.0 / bot;
             // The plain log-likelihood (no model output, no asymmetric veto, numpy boundary) gets its own loop: in
