@@ -11,9 +11,20 @@
 //               24 terms at |z| = 8 down to 4 from |z| = 1000, the bulk of a spectrum's pixels),
 //               its term-by-term derivative and that of z w (no cancellation)
 //
-// Accuracy (numpy restatement against 40-digit mpmath): |dw| <= 5e-15 |w|, |dw'| <= 2e-13 |w'|, e (below) <= 1e-15 relative
-// beyond |z| = 8, over |x| <= 3000, y in [1e-6, 10].  The 40 coefficients are Weideman's FFT of exp(-t^2)(L^2 + t^2) on
-// t = L tan(theta/2), highest degree first (his `cef` routine, evaluated in float64).
+// Accuracy, measured ON THE DEVICE against 120-digit mpmath (tests/test_gpu_voigt_grad.py; the 3871 points of
+// tests/golden/voigt_grad_reference.npz: y in {0, 1e-9 ... 30}, |x| <= 1e8, both sides of |z| = 8 and of every bracket of
+// asym_terms), worst case per region:
+//   |z| <  8 : |dw| <= 1.0e-15 |w|, |dw'| <= 6.0e-14 |w'| (complex; claimed: 5e-15, 2e-13); e, and the d2, e2, e3 of
+//              faddeeva_d2w, within 5.0 eps M_q, eps = 2^-53, M_q the magnitudes that the identity of q adds up
+//              (M_w' = 2|z||w| + 2/sqrt(pi), M_e = |w| + |z| M_w', ...).  As a fraction of the VALUE that is much more just
+//              inside |z| = 8 at small y: at y = 1e-4, 6 <= |x| < 8, e 4.0e-8, d2 4.0e-8, e2 1.1e-6, e3 3.9e-6
+//              (DESIGN section 3.8 has the table)
+//   |z| >= 8 : every output within 8.8e-16 of the magnitude of its complex quantity; as a fraction of the value itself
+//              wr, wi, dr, di, e2 <= 1.6e-15, and e 2.0e-15, d2 4.0e-15, e3 4.4e-15, worst next to the zeros of their real
+//              parts (Re (z w)' and Re w'' vanish on x = y/sqrt 3; asym_lead below).  exp(-x^2) <= 1.6e-28 is dropped, so
+//              at y = 0 the real parts are 0.
+// The 40 coefficients are Weideman's FFT of exp(-t^2)(L^2 + t^2) on t = L tan(theta/2), highest degree first (his `cef`
+// routine, evaluated in float64).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,8 +35,9 @@ constexpr int kWeidN = 40;
 constexpr double kGradInvSqrtPi = 0.56418958354775628695;
 constexpr double kAsymR2 = 64.0;      // |z|^2 from which the asymptotic series takes over
 
-// Terms of the asymptotic series that keep w, w' and (z w)' within 1e-15 relative over [|z|, next threshold) (checked against
-// 40-digit mpmath; the truncation error falls as |z| grows inside each bracket).  (z w)' starts at the k = 1 term, so its
+// Terms of the asymptotic series that keep w, w' and (z w)' within about 1e-15 relative over [|z|, next threshold) (on the device
+// against 120-digit mpmath at both edges of every bracket, see above; the truncation error falls as |z| grows inside each
+// bracket).  (z w)' starts at the k = 1 term, so its
 // relative truncation error is 2k|z|^2 times the last term's: that, not w, sets the counts.
 __device__ __forceinline__ int asym_terms(double r2) {
     return r2 >= 1e6 ? 4 : r2 >= 1e4 ? 6 : r2 >= 900.0 ? 9 : r2 >= 225.0 ? 14 : 24;
@@ -44,6 +56,15 @@ __device__ __constant__ static const double kWeidCoef[kWeidN] = {
     1.72538308481797786e+00, 2.20151379487831189e+00, 2.61605415276185971e+00, 2.89962450938970484e+00,
 };
 
+// Re (i / (sqrt(pi) z^3)) = y (3 x^2 - y^2) / (sqrt(pi) |z|^6), rr2 = 1/|z|^2, rm2 = 1/|z|^4: the leading term of the series of
+// (z w)' (times -1), of w'' (times 2) and of (z^2 w)''.  It vanishes on x = y / sqrt 3; taken as the real part of a complex
+// product it keeps there only ~1e-16 of the term's MAGNITUDE, which next to the zero left those three real parts with 1e-14
+// to 6e-14 of their value.  In real arithmetic, with the roundings of x^2 and y^2 put back, the difference is good to an ulp.
+__device__ __forceinline__ double asym_lead(double x, double y, double rr2, double rm2) {
+    const double p = y * y, pe = fma(y, y, -p), q = x * x, qe = fma(x, x, -q);
+    return y * (fma(3.0, q, -p) + (3.0 * qe - pe)) * kGradInvSqrtPi * rr2 * rm2;
+}
+
 // (wr, wi) = w(x + i y), (dr, di) = w'(x + i y), e = Re(w + z w') = H + x H_x + y H_y; y >= 0.
 // e is what d tau / d b needs; in the wings its terms cancel to O(1/|z|^2) of H (a damped line's Lorentzian wing does not
 // depend on b), so beyond |z| = 8 it is summed from its own series, (z w)' = i/sqrt(pi) sum_k -2k c_k z^(-2k-1).
@@ -60,7 +81,7 @@ __device__ __forceinline__ void faddeeva_dw(double x, double y, double& wr, doub
         for (int k = 0; k < nt; ++k) {
             sr += cr; si += ci;
             tr -= (2 * k + 1) * cr; ti -= (2 * k + 1) * ci;
-            er -= (2 * k) * cr; ei -= (2 * k) * ci;
+            if (k != 1) { er -= (2 * k) * cr; ei -= (2 * k) * ci; }     // (k = 1 is asym_lead)
             const double f = (double)(2 * k + 1);
             const double nr = f * (cr * hr - ci * hi), ni = f * (cr * hi + ci * hr);
             cr = nr; ci = ni;
@@ -69,7 +90,7 @@ __device__ __forceinline__ void faddeeva_dw(double x, double y, double& wr, doub
         const double ar = y * kGradInvSqrtPi * rr2, ai = x * kGradInvSqrtPi * rr2;
         wr = ar * sr - ai * si;
         wi = ar * si + ai * sr;
-        e = ar * er - ai * ei;
+        e = (ar * er - ai * ei) - asym_lead(x, y, rr2, rm2);
         // i/(sqrt(pi) z^2) = i conj(z^2) / (sqrt(pi) |z|^4)
         const double br = z2i * kGradInvSqrtPi * rm2, bi = z2r * kGradInvSqrtPi * rm2;
         dr = br * tr - bi * ti;
@@ -121,10 +142,11 @@ __device__ __forceinline__ void faddeeva_d2w(double x, double y, double& wr, dou
             const double f = (double)(2 * k + 1), g = (double)(2 * k);
             sr += cr; si += ci;
             tr -= f * cr; ti -= f * ci;
-            er -= g * cr; ei -= g * ci;
-            ur += f * (g + 2.0) * cr; ui += f * (g + 2.0) * ci;      // w''
-            pr += g * f * cr; pi += g * f * ci;                      // (z w)''
-            qr += g * (g - 1.0) * cr; qi += g * (g - 1.0) * ci;      // (z^2 w)''
+            // the term in 1/z^3 of (z w)', w'' and (z^2 w)'' is asym_lead
+            if (k != 1) { er -= g * cr; ei -= g * ci; }
+            if (k != 0) { ur += f * (g + 2.0) * cr; ui += f * (g + 2.0) * ci; }      // w''
+            pr += g * f * cr; pi += g * f * ci;                                      // (z w)''
+            if (k != 1) { qr += g * (g - 1.0) * cr; qi += g * (g - 1.0) * ci; }      // (z^2 w)''
             const double nr = f * (cr * hr - ci * hi), ni = f * (cr * hi + ci * hr);
             cr = nr; ci = ni;
         }
@@ -132,12 +154,13 @@ __device__ __forceinline__ void faddeeva_d2w(double x, double y, double& wr, dou
         const double ar = y * kGradInvSqrtPi * rr2, ai = x * kGradInvSqrtPi * rr2;
         const double br = z2i * kGradInvSqrtPi * rm2, bi = z2r * kGradInvSqrtPi * rm2;
         const double gr = (br * x + bi * y) * rr2, gi = (bi * x - br * y) * rr2;
+        const double lead = asym_lead(x, y, rr2, rm2);
         wr = ar * sr - ai * si;
-        e = ar * er - ai * ei;
-        e3 = ar * qr - ai * qi;
+        e = (ar * er - ai * ei) - lead;
+        e3 = (ar * qr - ai * qi) + lead;
         dr = br * tr - bi * ti;
         e2 = br * pr - bi * pi;
-        d2 = gr * ur - gi * ui;
+        d2 = (gr * ur - gi * ui) + 2.0 * lead;
         return;
     }
     double wi, di;

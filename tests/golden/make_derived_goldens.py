@@ -1,38 +1,162 @@
 #!/usr/bin/env python3
-"""Regenerate tests/golden/derived_goldens.json from the pinned oracle (CPU only)."""
+"""Regenerate the derived fixtures of tests/golden/ (CPU only).
+
+    make_derived_goldens.py               derived_goldens.json, from the pinned oracle
+    make_derived_goldens.py voigt_grad    voigt_grad_reference.npz, from mpmath (under a minute)
+"""
 import json
+import math
 import os
 import sys
+from fractions import Fraction
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", ".."))
-from oracle import numpy_oracle as o  # noqa: E402
 
-sys.path.insert(0, os.path.join(HERE, ".."))
-mc = __import__("importlib").import_module("mc-alf_amd.workloads")
 
-d = np.loadtxt(os.path.join(HERE, "civ_mock_spec_multicomp.txt"))
-prob10 = o.Problem(d[:, 0], d[:, 1], d[:, 2], o.CIV_LINES, (10, 10), specres=[8.0], fitrange=[[6180, 6220]])
-p = mc.truth_vector(10)
-model = o.reconstruct_spec(prob10, p)
-out = {
-    "G3_logL_truth": o.lnlhood_worker(prob10, p),
-    "G3_chi2_truth": o.chi2(prob10, p),
-    "G3_jaxsem_f64_logL_truth": o.jax_loglike_f64(prob10, p),
-    "G3_model_sha_sum": float(model.sum()),
-    "velstep": prob10.velstep,
-    "sigma_pix_R8": (8.0 / 2.354820) / prob10.velstep,
-    "n_R8": int(np.ceil(3.0348 * (8.0 / 2.354820) / prob10.velstep)),
-}
-# config A: 16 seeded draws and their oracle logL
-kw, _, seed = mc.config("A")
-P = mc.draw_P(kw, 16, np.random.default_rng(seed))
-probA = o.Problem(d[:, 0], d[:, 1], d[:, 2], o.CIV_LINES, (2, 2), specres=[8.0], Nrange=[12.0, 14.5],
-                  brange=[10.0, 40.0], zrange=[2.99, 3.01], fitrange=[[6180, 6220]])
-out["A_P16"] = P.tolist()
-out["A_logL16"] = o.loglike_batch(probA, P).tolist()
-with open(os.path.join(HERE, "derived_goldens.json"), "w") as fh:
-    json.dump(out, fh, indent=1)
-print(json.dumps({k: v for k, v in out.items() if not k.startswith("A_")}, indent=1))
+def make_derived_goldens():
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    from oracle import numpy_oracle as o  # noqa: E402
+
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    mc = __import__("importlib").import_module("mc-alf_amd.workloads")
+
+    d = np.loadtxt(os.path.join(HERE, "civ_mock_spec_multicomp.txt"))
+    prob10 = o.Problem(d[:, 0], d[:, 1], d[:, 2], o.CIV_LINES, (10, 10), specres=[8.0], fitrange=[[6180, 6220]])
+    p = mc.truth_vector(10)
+    model = o.reconstruct_spec(prob10, p)
+    out = {
+        "G3_logL_truth": o.lnlhood_worker(prob10, p),
+        "G3_chi2_truth": o.chi2(prob10, p),
+        "G3_jaxsem_f64_logL_truth": o.jax_loglike_f64(prob10, p),
+        "G3_model_sha_sum": float(model.sum()),
+        "velstep": prob10.velstep,
+        "sigma_pix_R8": (8.0 / 2.354820) / prob10.velstep,
+        "n_R8": int(np.ceil(3.0348 * (8.0 / 2.354820) / prob10.velstep)),
+    }
+    # config A: 16 seeded draws and their oracle logL
+    kw, _, seed = mc.config("A")
+    P = mc.draw_P(kw, 16, np.random.default_rng(seed))
+    probA = o.Problem(d[:, 0], d[:, 1], d[:, 2], o.CIV_LINES, (2, 2), specres=[8.0], Nrange=[12.0, 14.5],
+                      brange=[10.0, 40.0], zrange=[2.99, 3.01], fitrange=[[6180, 6220]])
+    out["A_P16"] = P.tolist()
+    out["A_logL16"] = o.loglike_batch(probA, P).tolist()
+    with open(os.path.join(HERE, "derived_goldens.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps({k: v for k, v in out.items() if not k.startswith("A_")}, indent=1))
+
+
+# ---- voigt_grad_reference.npz: the point set of tests/test_gpu_voigt_grad.py and its exact values ----------------------------
+#
+# Columns of `ref`, in the order of VG_NAMES: w, w', Re (z w)', Re w'', Re (z w)'', Re (z^2 w)'' at z = x + i y, which are what
+# the device functions return, then Im (z w)', Im (z w)'', Im (z^2 w)'' (the tests scale some bars with the complex magnitudes), from
+#     w = exp(-z^2) erfc(-i z),  w' = -2 z w + 2i/sqrt(pi),  E = w + z w',  w'' = -2 E,  (z w)'' = 2 w' + z w'',
+#     (z^2 w)'' = 2 E + z (z w)''
+# in mpmath at VG_DPS digits on the exact float64 x and y, rounded to float64 only at the end.  Every point is evaluated at
+# VG_DPS_CHECK digits too and refused if any component of the two differs by more than 1e-18 relative (the identities lose
+# over thirty digits in a far Lorentzian wing: 50 digits are not enough at |x| ~ 3e5, y = 1e-6, and 80 not at |x| ~ 7e7,
+# y = 1e-9, where Re (z^2 w)'' ~ 1e-41 comes out of terms ~ 1e-8 times a z^2 ~ 1e16).
+VG_NAMES = ("wr", "wi", "dr", "di", "e", "d2", "e2", "e3", "ei", "e2i", "e3i")
+VG_DPS, VG_DPS_CHECK = 120, 160
+VG_FILE = os.path.join(HERE, "voigt_grad_reference.npz")
+VG_Y = (0.0, 1e-9, 1e-6, 1e-4, 3e-4, 1e-3, 2.0 ** -8, 0.05, 0.5, 3.0, 10.0, 30.0)
+VG_THRESHOLDS = (64.0, 225.0, 900.0, 1e4, 1e6)          # kAsymR2 and the r^2 brackets of asym_terms (voigt_grad.h)
+
+
+def _r2_variants(a, b):
+    """a*a + b*b as float64 under every contraction a compiler may choose: none, fma(a, a, b*b), fma(b, b, a*a)."""
+    fa, fb = Fraction(a), Fraction(b)
+    return (a * a + b * b, float(fa * fa + Fraction(b * b)), float(Fraction(a * a) + fb * fb))
+
+
+def _edge(fixed, T):
+    """The free coordinate t around sqrt(T - fixed^2): the largest t with t^2 + fixed^2 < T, one with == T where a double
+    gives it, and the smallest with > T -- each under EVERY variant of _r2_variants, so that the device's branch at T does not
+    depend on how its compiler contracted the sum."""
+    t0 = math.sqrt(T - fixed * fixed)
+    cand = [t0]
+    for _ in range(64):
+        cand.append(math.nextafter(cand[-1], math.inf))
+    lo = t0
+    for _ in range(64):
+        lo = math.nextafter(lo, 0.0)
+        cand.insert(0, lo)
+    below = max(t for t in cand if all(v < T for v in _r2_variants(t, fixed)))
+    above = min(t for t in cand if all(v > T for v in _r2_variants(t, fixed)))
+    on = [t for t in cand if all(v == T for v in _r2_variants(t, fixed))]
+    assert cand[0] < below < above < cand[-1]
+    return [below] + on[len(on) // 2:len(on) // 2 + 1] + [above]
+
+
+def voigt_grad_points():
+    """(x, y) of the fixture.  Per y of VG_Y:
+      core    160 values of x on [0, 8) clustered towards 8, x_k = 8 (1 - (1 - k/160)^2), plus 7.9999 and the largest double
+              that keeps r^2 < 64 (for y = 10 and 30 these are series points: the seam reached through y)
+      edges   for every threshold T of VG_THRESHOLDS above y^2: r^2 just below T, on T where a double gives it, just above
+      wing    120 log-spaced x from 8 to 1e8
+      signs   the negative of every tenth of these x (x = 0 is the first core value)
+    and the seam through y at (0, 8) and around (5, sqrt 39)."""
+    core = [8.0 * (1.0 - (1.0 - k / 160.0) ** 2) for k in range(160)]
+    wing = [float(v) for v in np.geomspace(8.0, 1e8, 120)]
+    X, Y = [], []
+    for y in VG_Y:
+        xs = core + [7.9999]
+        for T in VG_THRESHOLDS:
+            if y * y < T:
+                xs += _edge(y, T)
+        xs += wing
+        xs += [-v for v in xs[5::10]]
+        X += xs
+        Y += [y] * len(xs)
+    X.append(0.0)
+    Y.append(8.0)
+    for y in _edge(5.0, 64.0):
+        X.append(5.0)
+        Y.append(y)
+    X, Y = np.array(X), np.array(Y)
+    for x, y in zip(X.tolist(), Y.tolist()):                 # no point's side of the seam depends on the contraction
+        v = _r2_variants(x, y)
+        assert all(t >= 64.0 for t in v) or all(t < 64.0 for t in v), (x, y)
+    return X, Y
+
+
+def voigt_grad_exact(x, y, dps):
+    """The quantities of VG_NAMES at the float64 point (x, y) as mpmath numbers of `dps` digits."""
+    import mpmath as mp
+    with mp.workdps(dps):
+        z = mp.mpc(mp.mpf(x), mp.mpf(y))
+        w = mp.exp(-z * z) * mp.erfc(-1j * z)
+        wp = -2 * z * w + 2j / mp.sqrt(mp.pi)
+        E = w + z * wp
+        w2 = -2 * E
+        zw2 = 2 * wp + z * w2
+        z2w2 = 2 * E + z * zw2
+        return (w.real, w.imag, wp.real, wp.imag, E.real, w2.real, zw2.real, z2w2.real, E.imag, zw2.imag, z2w2.imag)
+
+
+def voigt_grad_reference(x, y, dps=VG_DPS):
+    """voigt_grad_exact rounded to float64."""
+    return [float(v) for v in voigt_grad_exact(x, y, dps)]
+
+
+def make_voigt_grad_goldens():
+    import mpmath as mp
+    X, Y = voigt_grad_points()
+    ref = np.empty((X.size, len(VG_NAMES)))
+    for i, (x, y) in enumerate(zip(X.tolist(), Y.tolist())):
+        lo, hi = voigt_grad_exact(x, y, VG_DPS), voigt_grad_exact(x, y, VG_DPS_CHECK)
+        with mp.workdps(VG_DPS_CHECK):
+            for name, a, b in zip(VG_NAMES, lo, hi):
+                if abs(a - b) > mp.mpf("1e-18") * abs(b):
+                    raise SystemExit("refused: %s at (%r, %r) differs between %d and %d digits" % (name, x, y, VG_DPS, VG_DPS_CHECK))
+        ref[i] = [float(v) for v in lo]
+    np.savez_compressed(VG_FILE, x=X, y=Y, ref=ref, dps=np.array([VG_DPS, VG_DPS_CHECK]))
+    print("%d points -> %s (%d bytes)" % (X.size, VG_FILE, os.path.getsize(VG_FILE)))
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] == ["voigt_grad"]:
+        make_voigt_grad_goldens()
+    else:
+        make_derived_goldens()

@@ -82,6 +82,26 @@ def test_voigt_hjerting_grad_against_scipy():
     assert np.all(np.abs(Hy + wp.imag) <= 1e-11 * np.abs(wp) + floor)
 
 
+def test_voigt_hjerting_grad_against_mpmath(tmp_path_factory):
+    """The entry on the points of tests/golden/voigt_grad_reference.npz, with the bars of tests/test_gpu_voigt_grad.py and no
+    |z|-scaled floor; and bit for bit what the probe of voigt_grad.h returns, which ties that probe to the shipped object."""
+    import voigt_grad_probe as vgp
+    fx = vgp.Fixture()
+    out = np.empty(3 * fx.n)
+    pd = C.POINTER(C.c_double)
+    rc = _lib.load().mcalf_voigt_hjerting_grad(fx.x.ctypes.data_as(pd), fx.y.ctypes.data_as(pd), fx.n, out.ctypes.data_as(pd), -1)
+    assert rc == 0
+    H, Hx, Hy = out.reshape(-1, 3).T
+    dH, dHx, dHy = np.abs(H - fx.ref["wr"]), np.abs(Hx - fx.ref["dr"]), np.abs(Hy + fx.ref["di"])
+    s = fx.series
+    for name, err, q in (("H", dH, "wr"), ("H_x", dHx, "dr"), ("H_y", dHy, "di")):
+        assert not vgp.worst(err, 1e-14 * np.abs(fx.ref[q]) + 1e-22, s, fx, "entry, series %s" % name).any(), name
+    assert not vgp.worst(dH, 5e-15 * fx.cabs["wr"], fx.core, fx, "entry, core H").any()
+    assert not vgp.worst(np.hypot(dHx, dHy), 2e-13 * fx.cabs["dr"], fx.core, fx, "entry, core (H_x, H_y)").any()
+    dev = vgp.run_probe(vgp.load_probe(tmp_path_factory.mktemp("voigt_grad_probe")), fx.x, fx.y)
+    assert np.array_equal(H, dev["wr"]) and np.array_equal(Hx, dev["dr"]) and np.array_equal(Hy, -dev["di"])
+
+
 def test_grad_G1_and_config_A():
     kw = _g1()
     P = np.array([[1.0, 13.8, 3.0, 15.0], [1.0, 13.5, 3.0002, 22.0], [1.0, 14.2, 2.9995, 9.0]])
