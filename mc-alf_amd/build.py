@@ -16,8 +16,10 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 KERNEL_SOURCE = "kernels.hip"
-# what the DEVICE code of the likelihood is made of: the kernel-source hash covers exactly these
-HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h"]
+# what the DEVICE code of the likelihood is made of -- kernels.hip and every header it includes, directly or through another
+# (the stages of the fused kernel are a header each: ONE translation unit) -- the kernel-source hash covers exactly these
+HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h", "wave_util.h", "sample_setup.h", "stream_handover.h",
+          "line_eval.h", "fused_item.h", "wide_lsf.h"]
 # Every device object: its source and the headers it includes.  Only kernels.hip's are hashed: the fused kernel includes none
 # of the others' own files (eqw_kernels.hip shares the hashed Voigt function, voigt_device.h and voigt_tables.h, with it).
 DEVICE_OBJECTS = {
@@ -64,7 +66,7 @@ def _stale(target: str, deps) -> bool:
 
 
 def source_hash() -> str:
-    """sha256 over the kernel sources (kernels.hip, kernel_args.h, voigt_device.h, voigt_tables.h), 16 hex digits.  The
+    """sha256 over the kernel sources (HASHED: kernels.hip and the headers it is built from), 16 hex digits.  The
     library carries it (mcalf_version()), the PMC-derived files under profiles/ are stamped with it, and bench.py drops
     their figures when the two differ -- a kernel edit cannot ship stale utilisation numbers, and an edit of the host
     side of the C ABI (the .cpp files) does not change what the counters measured."""

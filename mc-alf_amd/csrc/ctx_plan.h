@@ -81,15 +81,12 @@ inline int check_spec(const mcalf_spec* sp, std::string* msg) {
 }
 
 // ---- the geometry ---------------------------------------------------------------------------------------------------------
-// LDS doubles of a workgroup next to its tile region: the folded tables of two barriers' lines, the records, the taps, the
-// reduction slots, the interpolation weights.
-inline size_t fixed_doubles(int lps, int ncl_cap, int n_cap) {
-    return 2 * (size_t)lps * kTabPad + (size_t)ncl_cap * kRecStride + (2 * (size_t)n_cap + 8) + kRedDoubles + 64 * VT_INODES;
-}
+// The LDS of a workgroup is laid out by ItemLds (kernel_args.h), the kernel's own carve-up: the folded tables of two barriers'
+// lines, the records, the taps, the reduction slots, the interpolation weights, then the tile region.
 // Pixels (tile and halo) a workgroup can hold: the tile region has ONE size (tile_doubles), so it is all of kExtMax when the
 // fixed part and the region fit the budget, and nothing otherwise.
 inline size_t tile_extent(int lps, int ncl_cap, int n_cap) {
-    return (fixed_doubles(lps, ncl_cap, n_cap) + tile_doubles(kExtMax)) * sizeof(double) > kLdsBudget ? 0 : (size_t)kExtMax;
+    return ItemLds(lps, ncl_cap, n_cap).bytes(kExtMax) > kLdsBudget ? 0 : (size_t)kExtMax;
 }
 // Lines per barrier: 5 when that saves a barrier at the context's largest line count and the extra folded tables cost no
 // tile pixels (LDS), else 4.
@@ -173,9 +170,8 @@ inline int plan_shape(const mcalf_spec& sp, int lines_per_sync, CtxShape* out, s
     if (!lsf_fits_tile(s.lps, s.ncl_cap, s.n_cap))
         return plan_fail(msg, MCALF_ERR_RANGE, "%d component-lines do not fit the %zu-byte LDS budget", s.ncl_cap, kLdsBudget);
     plan_tiling(s.npix, tile_extent(s.lps, s.ncl_cap, s.n_cap), s.n_cap, &s.tile, &s.ntiles);
-    const size_t region = (size_t)tile_doubles(s.tile + 2 * s.n_cap);
-    s.lds_bytes = (fixed_doubles(s.lps, s.ncl_cap, s.n_cap) + region) * sizeof(double);
-    s.lds_bytes_inline = (fixed_doubles(4, s.ncl_cap, s.n_cap) + region) * sizeof(double);
+    s.lds_bytes = ItemLds(s.lps, s.ncl_cap, s.n_cap).bytes(s.tile + 2 * s.n_cap);
+    s.lds_bytes_inline = ItemLds(4, s.ncl_cap, s.n_cap).bytes(s.tile + 2 * s.n_cap);
     s.selfhalo = (s.ntiles == 1 && s.n_cap < s.npix) ? 1 : 0;
     return MCALF_OK;
 }

@@ -167,6 +167,23 @@ constexpr int tile_doubles(int) {
     return 8 * kPlaneStride > VT_NY * VT_NTOT ? 8 * kPlaneStride : VT_NY * VT_NTOT;   // the region doubles as the T table
 }
 
+// The dynamic LDS of a workgroup of the fused kernel, as offsets in doubles from its start: the ONE definition that the
+// kernel carves its shared memory with (fused_item.h) and that the host sizes the launch, the lines per barrier and the
+// resident kernel's row offset from (ctx_plan.h).  lps: lines folded per barrier.
+struct ItemLds {
+    long tab;        // 2 x lps folded tables (kTabPad each), double-buffered
+    long rec;        // ncl_cap records of kRecStride
+    long taps;       // 2 n_cap + 8: the LSF taps, zero-padded to a multiple of 8
+    long red;        // kRedDoubles: 3 * kWaves partials + the next item index
+    long wt;         // [VT_INODES][64] interpolation weights, node-major
+    long tile;       // the flux tile (tile_doubles), which holds the universal table T until the component loop ends
+    constexpr ItemLds(int lps, int ncl_cap, int n_cap)
+        : tab(0), rec(tab + 2 * (long)lps * kTabPad), taps(rec + (long)ncl_cap * kRecStride), red(taps + 2 * (long)n_cap + 8),
+          wt(red + kRedDoubles), tile(wt + 64 * VT_INODES) {}
+    constexpr size_t doubles(int ext) const { return (size_t)tile + (size_t)tile_doubles(ext); }   // with a tile region of `ext` pixels
+    constexpr size_t bytes(int ext) const { return doubles(ext) * sizeof(double); }
+};
+
 constexpr int kSetupBlockMax = 512;
 constexpr int kMinWaves = 4;            // waves per SIMD the fused kernel is compiled for (2 workgroups of 8 waves per CU)
 

@@ -96,6 +96,52 @@ static const Case kCases[] = {
     {"bad-specres-inf", "specres_max infinite", 600, "log", 2.0, 2, 2, 1, 1, 8.0, -1.0, 0, -1, kNone},
 };
 
+// The LDS doubles of a workgroup in front of its tile region (ItemLds::tile: tables, records, taps, reduction slots, weights),
+// at the case's lines per barrier and at the one-launch variant's 4: what the planner's own hand-written sum gave for
+// every case that plans, recorded before the kernel's layout (kernel_args.h) took its place.
+struct FixedLds {
+    const char* name;
+    long at_lps, at_4;
+};
+static const FixedLds kFixedLds[] = {
+    {"log1", 4798, 3958},      {"log7", 4798, 3958},       {"log8", 4798, 3958},           {"log9", 4798, 3958},
+    {"log63", 4798, 3958},     {"log64", 4798, 3958},      {"log65", 4798, 3958},          {"log66", 4798, 3958},
+    {"log128", 4798, 3958},    {"log130", 4798, 3958},     {"log4000", 4798, 3958},        {"linear130", 4798, 3958},
+    {"gap700", 4798, 3958},    {"descending4000", 4798, 3958}, {"shuffled4000", 4798, 3958}, {"tile4080", 4798, 3958},
+    {"tile4081", 4798, 3958},  {"tiles3", 4798, 3958},     {"tile4096", 4786, 3946},       {"reach0", 4786, 3946},
+    {"reach-fixed", 4826, 3986}, {"reach-free", 4798, 3958}, {"jax0", 4790, 3950},         {"jax32", 4850, 4010},
+    {"jax-f32", 4798, 3958},   {"numpy-f64", 4800, 3960},  {"fit971", 5856, 5856},         {"wide972", 3914, 3914},
+    {"wide2016", 3914, 3914},  {"wide2017", 3914, 3914},   {"wide-jax", 3914, 3914},       {"wide-short", 3914, 3914},
+    {"lps-4lines", 3950, 3950}, {"lps-5lines", 4798, 3958}, {"lps-137", 5854, 5014},       {"lps-138", 5022, 5022},
+    {"lps-env4", 3958, 3958},  {"lps-env5", 4790, 3950},   {"lps-env5-refused", 5022, 5022}, {"lps-env7", 4798, 3958},
+    {"ncl242", 5854, 5854},    {"ncl243", 5850, 5850},     {"ncl243-reach0", 5850, 5850},
+};
+
+// 0 when the layout of a planned shape gives the recorded doubles and the shape's LDS sizes follow from it; a line on
+// stderr and 1 otherwise (the test takes any as a failure).
+static int check_layout(const char* name, const CtxShape& s) {
+    const FixedLds* want = nullptr;
+    for (const FixedLds& f : kFixedLds)
+        if (std::strcmp(f.name, name) == 0) want = &f;
+    if (!want) {
+        std::fprintf(stderr, "%s: plans, and has no recorded LDS layout\n", name);
+        return 1;
+    }
+    const ItemLds at_lps(s.lps, s.ncl_cap, s.n_cap), at_4(4, s.ncl_cap, s.n_cap);
+    const size_t region = (size_t)tile_doubles(s.tile + 2 * s.n_cap);
+    const bool ok = at_lps.tile == want->at_lps && at_4.tile == want->at_4 &&
+                    s.lds_bytes == ((size_t)want->at_lps + region) * sizeof(double) &&
+                    s.lds_bytes_inline == ((size_t)want->at_4 + region) * sizeof(double) &&
+                    // the regions follow each other without a gap, in the kernel's order
+                    at_lps.tab == 0 && at_lps.rec == 2L * s.lps * kTabPad && at_lps.taps - at_lps.rec == (long)s.ncl_cap * kRecStride &&
+                    at_lps.red - at_lps.taps == 2L * s.n_cap + 8 && at_lps.wt - at_lps.red == kRedDoubles &&
+                    at_lps.tile - at_lps.wt == 64 * VT_INODES;
+    if (!ok)
+        std::fprintf(stderr, "%s: LDS layout gives %ld / %ld doubles (lds_bytes %zu / %zu), recorded %ld / %ld\n", name, at_lps.tile, at_4.tile,
+                     s.lds_bytes, s.lds_bytes_inline, want->at_lps, want->at_4);
+    return ok ? 0 : 1;
+}
+
 static std::vector<double> make_wl(const char* grid, long n) {
     std::vector<double> wl(n);
     const std::string g = grid;
@@ -130,6 +176,7 @@ static std::string quoted(const std::string& s) {
 }
 
 int main() {
+    int bad = 0;
     for (const Case& c : kCases) {
         const long nalloc = c.npix > 0 && c.npix <= 100000 ? c.npix : 1;       // (a refused npix never has its arrays read)
         std::vector<double> wl = make_wl(c.grid, nalloc), flux(nalloc, 1.0), err(nalloc);
@@ -164,6 +211,7 @@ int main() {
         int rc = check_spec(c.defect == kNullSpec ? nullptr : &sp, &msg);
         const bool checked = rc == MCALF_OK;
         if (checked && (rc = plan_shape(sp, c.lps_env, &s, &msg)) == MCALF_OK) plan_tables(sp, &s, &t);
+        if (rc == MCALF_OK) bad += check_layout(c.name, s);
 
         std::printf("{\"name\": %s, \"why\": %s, \"spec\": {\"npix\": %ld, \"grid\": \"%s\", \"velstep\": \"%a\", \"nlines\": %d, \"ncompmax\": %d, "
                     "\"nfill\": %d, \"freespecres\": %d, \"specres_fixed\": \"%a\", \"specres_max\": \"%a\", \"conv_mode\": %d, \"lps_env\": %d, "
@@ -188,5 +236,5 @@ int main() {
         }
         std::printf("}\n");
     }
-    return 0;
+    return bad ? 1 : 0;
 }

@@ -1,6 +1,7 @@
 """CPU: the workload selection and bookkeeping helpers of bench.py (no GPU, nothing is launched)."""
 import json
 import os
+import re
 import sys
 
 import pytest
@@ -59,8 +60,18 @@ def test_library_carries_the_hash_of_the_device_sources():
     lib = mcalf_amd._lib.load()
     assert bench.library_source_hash(lib) == bld.source_hash()            # built by __graft_entry__.build()
     # the hash covers what the DEVICE code is made of -- the kernels, the argument block they share with the host, the
-    # Voigt function and its tables -- and none of the host side of the C ABI
-    assert bld.HASHED == ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h"]
+    # Voigt function and its tables, the stage headers of the fused kernel -- and none of the host side of the C ABI:
+    # kernels.hip and every "..." header that can be reached from it, no more and no fewer
+    reached, todo = [], ["kernels.hip"]
+    while todo:
+        f = todo.pop()
+        if f not in reached:
+            reached.append(f)
+            todo += re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(bld.CSRC, f)).read(), re.M)
+    assert bld.HASHED[0] == "kernels.hip" and len(set(bld.HASHED)) == len(bld.HASHED)
+    assert sorted(bld.HASHED) == sorted(reached)
+    assert {"kernel_args.h", "voigt_device.h", "voigt_tables.h"} < set(bld.HASHED)
+    assert bld.DEVICE_OBJECTS["kernels.hip"] == bld.HASHED[1:]
     assert not set(bld.HASHED) & set(bld.HOST_SOURCES)
     kernels = open(os.path.join(bld.CSRC, "kernels.hip")).read()
     assert 'extern "C"' not in kernels and "__global__" in kernels

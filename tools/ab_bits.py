@@ -2,8 +2,8 @@
 """A/B of two builds of the library: every plan of the likelihood's entries once, each case in a FRESH context, each build in a
 process of its own (MCALF_HIP_LIB); outputs compared bit for bit and the whole mcalf_last_launch record field by field.
 
-    python tools/explore/ab_bits.py libA.so libB.so      # exit status 1 when anything differs
-    python tools/explore/ab_bits.py --child out.json     # the cases alone, with the library MCALF_HIP_LIB names (e.g. under a profiler)
+    python tools/ab_bits.py libA.so libB.so      # exit status 1 when anything differs
+    python tools/ab_bits.py --child out.json     # the cases alone, with the library MCALF_HIP_LIB names (e.g. under a profiler)
 
 Cases: the device entry (one block, three blocks), the zero-copy small call, the streaming launch, the row-block pipeline
 (MCALF_STREAM=0), chi2, model and single-component output, the cube entry (small, streaming, staged), a wide-LSF context,
@@ -13,7 +13,7 @@ import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def child(path):
