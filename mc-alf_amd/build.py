@@ -24,10 +24,10 @@ HASHED = ["kernels.hip", "kernel_args.h", "voigt_device.h", "voigt_tables.h", "w
 # of the others' own files (eqw_kernels.hip shares the hashed Voigt function, voigt_device.h and voigt_tables.h, with it).
 DEVICE_OBJECTS = {
     KERNEL_SOURCE: HASHED[1:],
-    "grad_kernels.hip": ["grad_args.h", "voigt_grad.h", "kernel_args.h", "voigt_tables.h"],
-    "eqw_kernels.hip": ["eqw_args.h", "voigt_device.h", "kernel_args.h", "voigt_tables.h"],
+    "grad_kernels.hip": ["grad_args.h", "theta_row.h", "voigt_grad.h", "kernel_args.h", "voigt_tables.h"],
+    "eqw_kernels.hip": ["eqw_args.h", "theta_row.h", "voigt_device.h", "wave_row.h", "kernel_args.h", "voigt_tables.h"],
     "band_kernels.hip": ["band_args.h", "kernel_args.h"],
-    "fit_kernels.hip": ["fit_args.h", "wave_row.h", "kernel_args.h"],
+    "fit_kernels.hip": ["fit_args.h", "theta_row.h", "wave_row.h", "kernel_args.h"],
     "ns_kernels.hip": ["ns_args.h", "wave_row.h", "prior_device.h", "prior_args.h", "kernel_args.h"],
     "ens_kernels.hip": ["ens_args.h", "wave_row.h", "prior_device.h", "prior_args.h", "kernel_args.h"],
     "prior_kernels.hip": ["prior_args.h", "prior_device.h", "wave_row.h", "kernel_args.h"],
@@ -38,7 +38,7 @@ REPORTED = [s for s in DEVICE_SOURCES if s != "grad_kernels.hip"]
 HOST_SOURCES = ["host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp",
                 "host_staged.cpp", "host_grad.cpp", "host_fit.cpp", "host_ns.cpp", "host_ens.cpp", "host_prior.cpp", "host_eqw.cpp", "host_band.cpp", "broker.cpp", "comm.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
-HOST_HEADERS = ["host_ctx.h", "ctx_plan.h", "kernel_args.h", "grad_args.h", "eqw_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ens_args.h", "prior_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
+HOST_HEADERS = ["host_ctx.h", "ctx_plan.h", "kernel_args.h", "theta_row.h", "grad_args.h", "eqw_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ens_args.h", "prior_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
 TARGET = os.path.join(CSRC, "libmcalf_hip.so")
 OBJDIR = os.path.join(CSRC, "obj")
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
@@ -139,7 +139,8 @@ def build(force: bool = False, verbose: bool = False, testing: bool = False, tar
 
 def build_tree(workdir: str, target: str, stamp: str = "patched-copy", defines=(), kernel_flags=(), report: bool = False) -> str:
     """Compile a COPY of the sources (tools/make_acc_build.py and friends patch one: the product source carries no
-    instrumentation) into `target`; with `report` the kernels' resource usage is returned instead of the path."""
+    instrumentation) into `target`; with `report` the resource usage of every device file's kernels is returned instead of the
+    path (resource_table picks a family by a part of its kernels' names)."""
     hipcc = _hipcc()
     objs = []
     log = ""
@@ -148,14 +149,14 @@ def build_tree(workdir: str, target: str, stamp: str = "patched-copy", defines=(
         if src == KERNEL_SOURCE:
             cmd = [hipcc] + KERNEL_FLAGS + list(kernel_flags) + (["-Rpass-analysis=kernel-resource-usage"] if report else [])
         elif src in DEVICE_SOURCES:
-            cmd = [hipcc] + KERNEL_FLAGS
+            cmd = [hipcc] + KERNEL_FLAGS + (["-Rpass-analysis=kernel-resource-usage"] if report else [])
         else:
             cmd = [hipcc] + HOST_FLAGS + [f'-DMCALF_SRC_HASH="{stamp}"']
         res = subprocess.run(cmd + [f"-D{d}" for d in defines] + ["-c", src, "-o", obj], cwd=workdir, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError("hipcc failed on %s:\n%s" % (src, res.stderr[-4000:]))
-        if src == KERNEL_SOURCE:
-            log = res.stderr
+        if src in DEVICE_SOURCES:
+            log += res.stderr
         objs.append(obj)
     res = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs + ["-ldl"], cwd=workdir,
                          capture_output=True, text=True)

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "kernel_args.h"
+#include "theta_row.h"
 
 namespace mcalf {
 
@@ -18,9 +19,9 @@ constexpr int kEqwRec = 8;                        // doubles per (slot, line) re
 constexpr int kEqwIndexLayout = 0, kEqwIndexAsWritten = 1;   // MCALF_EQW_LAYOUT / MCALF_EQW_AS_WRITTEN of the C ABI
 // a record's kind: how the pixel kernel evaluates it
 constexpr double kEqwInactive = 0.0;              // layout mode, slot at or beyond the row's active count: cell exactly 0, parameters never read
-constexpr double kEqwFast = 1.0;                  // the y-folded tables
-constexpr double kEqwGeneral = 2.0;               // hjert_general: a outside [0, 2^-8], absurd columns
-constexpr double kEqwZero = 3.0;                  // |1 + z| beyond 1e100: every |u| overflows, tau = 0 (kernels.hip: build_line_record)
+constexpr double kEqwFast = kRecFast;             // the y-folded tables
+constexpr double kEqwGeneral = kRecGeneral;       // hjert_general: a outside [0, 2^-8], absurd columns
+constexpr double kEqwZero = kRecZero;             // |1 + z| beyond 1e100: every |u| overflows, tau = 0 (theta_row.h: record_kind)
 
 // One pass over `nrows` rows of a batch.
 struct EqwArgs {
@@ -33,7 +34,8 @@ struct EqwArgs {
                               //   cell c * nlines + l = component c, line l; cell ncompmax * nlines + l = the blend of line l
     double* Wcomp;            // [nrows, ncompmax, nlines] or nullptr
     double* Wblend;           // [nrows, nlines] or nullptr
-    int nrows, npix, ndim, ntiles, nlines, ncompmax, startind, jax, indexing;
+    int nrows, npix, ntiles, indexing;
+    RowLayout lay;            // how a row of P is read (theta_row.h)
 };
 
 // The kernels of eqw_kernels.hip; all take (const EqwArgs a).

@@ -5,8 +5,8 @@
 //     Wblend[l]    =   sum_pix (1 - exp(-sum_c tau_cl(pix))) dlam[pix]
 //
 // tau is the likelihood's: the y-folded tables of voigt_device.h for a in [0, 2^-8], hjert_general for everything else
-// (a negative "b" of the as-written indexing, absurd columns), and the same record arithmetic as kernels.hip's
-// build_line_record.  Nothing is convolved and the continuum does not enter (the reference's (cont v) / cont).
+// (a negative "b" of the as-written indexing, absurd columns), and the record arithmetic of theta_row.h (line_scale,
+// record_kind).  Nothing is convolved and the continuum does not enter (the reference's (cont v) / cont).
 //
 //   setup     one workgroup per row: the slots decoded under a.indexing, one record per (slot, line)
 //   pixel     workgroup = (row, tile of kEqwTile pixels).  Lines outer, slots inner, so the blend needs ONE running sum
@@ -22,16 +22,18 @@
 
 #include "eqw_args.h"
 #include "voigt_device.h"
+#include "wave_row.h"
 
 using namespace mcalf;
 
 namespace {
 
+static_assert(kFastMaxA == kYFastMax, "record_kind's fast path is the folded tables' range of a");
 constexpr int kEqwTab = (VT_NTOT + 7) & ~7;       // doubles per folded table in LDS
 static_assert(2 * kEqwBlock >= VT_NTOT, "two coefficients per thread cover the table");
 
-__device__ __forceinline__ int eqw_nrec(const EqwArgs& a) { return a.ncompmax * a.nlines; }
-__device__ __forceinline__ int eqw_ncells(const EqwArgs& a) { return (a.ncompmax + 1) * a.nlines; }
+__device__ __forceinline__ int eqw_nrec(const EqwArgs& a) { return a.lay.ncompmax * a.lay.nlines; }
+__device__ __forceinline__ int eqw_ncells(const EqwArgs& a) { return (a.lay.ncompmax + 1) * a.lay.nlines; }
 
 // K H(u, y) of a fast-path line from its folded table: what a directly evaluated pixel of the fused kernel gets
 // (kernels.hip: eval_line) -- the core table for every |u| < 8, the two wing zones in 1/u^2 beyond.
@@ -63,13 +65,6 @@ __device__ __forceinline__ double tau_fast(const double* __restrict__ tab, doubl
     return t * P;
 }
 
-// Sum over the wave's 64 lanes, the same butterfly every time (every lane gets the result).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // sum_j (1 - exp(-tau_j)) dlam_j over the thread's valid pixels, in pixel order.
 __device__ __forceinline__ double width_terms(const double (&tau)[kEqwPpt], const double (&dl)[kEqwPpt], unsigned valid) {
     double w = 0.0;
@@ -82,43 +77,29 @@ __device__ __forceinline__ double width_terms(const double (&tau)[kEqwPpt], cons
 
 __global__ __launch_bounds__(64) void mcalf_eqw_setup_kernel(const EqwArgs a) {
     const int r = blockIdx.x;
-    const double* p = a.P + (size_t)r * a.ndim;
+    const double* p = a.P + (size_t)r * a.lay.ndim;
     const bool layout = a.indexing == kEqwIndexLayout;
-    int nc = a.ncompmax;                                                          // as written: every slot (:481)
-    if (layout) {
-        const double ncv = p[a.startind];
-        const double nct = a.jax ? floor(ncv) : trunc(ncv);                      // :428 int() / :616 floor
-        nc = (nct >= 1.0) ? ((nct >= (double)a.ncompmax) ? a.ncompmax : (int)nct) : 0;
-    }
+    const int nc = layout ? active_components(a.lay, p[a.lay.startind]) : a.lay.ncompmax;   // as written: every slot (:481)
     const int nrec = eqw_nrec(a);
     for (int k = threadIdx.x; k < nrec; k += 64) {
-        const int c = k / a.nlines;
+        const int c = k / a.lay.nlines;
         double* rec = a.recs + ((size_t)r * nrec + k) * kEqwRec;
         if (c >= nc) {                                                             // its parameters are never read
 #pragma unroll
             for (int i = 0; i < kEqwRec; ++i) rec[i] = 0.0;                        // (kind = kEqwInactive)
             continue;
         }
-        const LineDev ln = a.lines[k - c * a.nlines];
-        const int q = a.startind + 3 * c + (layout ? 1 : 0);                       // :431 (N, z, b) / :482 as written
+        const LineDev ln = a.lines[k - c * a.lay.nlines];
+        const int q = target_col(a.lay, c) - (layout ? 0 : 1);                     // as written: one column early (:482)
         const double logN = p[q], z = p[q + 1], b = p[q + 2];
-        // the arithmetic of kernels.hip: build_line_record
-        const double cold = pow(10.0, logN);                                       // :357
-        const double zp1 = z + 1.0;                                                // :358
-        const double rdnu = ln.wrest_cm / (b * 1e5);                               // 1/dnu (:360, :376)
-        const double av = ln.gamma4pi * rdnu;                                      // :361
-        const double K = kTauConst * cold * ln.f * rdnu;                           // :364-365
-        double kind = kEqwFast;
-        if (!(av <= kYFastMax) || !(av >= 0.0)) kind = kEqwGeneral;                // (also NaN)
-        else if (K * 1.6e-28 > 2e-17) kind = kEqwGeneral;                          // exp(-x^2) matters past |x| = 8
-        if (!(fabs(zp1) < 1e100) && zp1 == zp1 && fabs(K) < 1e100 && fabs(av) < 1e100) kind = kEqwZero;
-        rec[0] = zp1 * rdnu;                                                       // u = nu A - B (:362)
-        rec[1] = ln.nujk * rdnu;
-        rec[2] = av;
-        rec[3] = K;
-        rec[4] = K * av * kInvSqrtPi;
-        rec[5] = kind;
-        rec[6] = zp1;
+        const LineScale s = line_scale(z, b, ln, pow(10.0, logN));
+        rec[0] = s.A;                                                              // u = nu A - B
+        rec[1] = s.B;
+        rec[2] = s.a;
+        rec[3] = s.K;
+        rec[4] = s.K * s.a * kInvSqrtPi;
+        rec[5] = (double)record_kind(s.zp1, s.a, s.K);
+        rec[6] = s.zp1;
         rec[7] = 0.0;
     }
 }
@@ -151,12 +132,12 @@ __global__ __launch_bounds__(kEqwBlock) void mcalf_eqw_pixel_kernel(const EqwArg
     double* part = a.part + ((size_t)r * a.ntiles + blockIdx.x) * eqw_ncells(a) * kEqwWaves;
     const bool wantComp = a.Wcomp != nullptr, wantBlend = a.Wblend != nullptr;
     int buf = 0;
-    for (int l = 0; l < a.nlines; ++l) {
+    for (int l = 0; l < a.lay.nlines; ++l) {
         double st[kEqwPpt];                                                        // running sum of tau over the slots, per pixel
 #pragma unroll
         for (int j = 0; j < kEqwPpt; ++j) st[j] = 0.0;
-        for (int c = 0; c < a.ncompmax; ++c) {
-            const int cell = c * a.nlines + l;
+        for (int c = 0; c < a.lay.ncompmax; ++c) {
+            const int cell = c * a.lay.nlines + l;
             const double* rec = recs + (size_t)cell * kEqwRec;
             const int kind = __builtin_amdgcn_readfirstlane((int)rec[5]);          // the same for the whole workgroup: a scalar branch
             if (kind != (int)kEqwFast && kind != (int)kEqwGeneral) continue;
@@ -212,7 +193,7 @@ __global__ __launch_bounds__(256) void mcalf_eqw_finalize_kernel(const EqwArgs a
             for (int k = 0; k < kEqwWaves; ++k) s += w[k];
         }
     }
-    if (!comp) a.Wblend[(size_t)r * a.nlines + (cell - nrec)] = s;
+    if (!comp) a.Wblend[(size_t)r * a.lay.nlines + (cell - nrec)] = s;
     else a.Wcomp[(size_t)r * nrec + cell] = (kind == kEqwInactive) ? 0.0 : s / zp1;    // :489
 }
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "kernel_args.h"
+#include "theta_row.h"
 
 namespace mcalf {
 
@@ -35,8 +36,9 @@ struct FitArgs {
     unsigned int* live;       // rows still live after the accept kernel (integer counter)
     double* dM;               // weight kernel: [nrows, npix], dM <- W (.) dM
     const double* W;          // [npix]
-    int nrows, ndim, npix, startind, ncompmax, jax;
+    int nrows, npix;
     double lambda0, ftol;
+    RowLayout lay;            // how a row is read (theta_row.h); the weight kernel does not look at it
 };
 
 // The kernels of fit_kernels.hip; all take (const FitArgs a).

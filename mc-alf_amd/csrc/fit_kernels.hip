@@ -19,32 +19,18 @@ using namespace mcalf;
 
 namespace {
 
-// Active components of a row, as the likelihood decodes the ncomp slot (int() on the numpy path, floor on the JAX path).
-__device__ __forceinline__ int active_count(const FitArgs& a, const double* th) {
-    const double ncv = th[a.startind];
-    const double nct = a.jax ? floor(ncv) : trunc(ncv);
-    return (nct >= 1.0) ? ((nct >= (double)a.ncompmax) ? a.ncompmax : (int)nct) : 0;
-}
-
-// Whether the fit may change coordinate k at all: not the ncomp slot, not the (N, z, b) of a slot at or beyond the active count.
-__device__ __forceinline__ bool movable(const FitArgs& a, int nc, int k) {
-    if (k == a.startind) return false;
-    const int rel = k - a.startind - 1;
-    return !(rel >= 3 * nc && rel < 3 * a.ncompmax);
-}
-
 __device__ __forceinline__ double clamp_keep_nan(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 }  // namespace
 
 __global__ __launch_bounds__(kFitWave) void mcalf_fit_start_kernel(const FitArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    const double* p0 = a.P0 + (size_t)row * a.ndim;
-    double* th = a.th + (size_t)row * a.ndim;
-    const int nc = active_count(a, p0);
-    for (int k = lane; k < a.ndim; k += kFitWave) {
+    const double* p0 = a.P0 + (size_t)row * a.lay.ndim;
+    double* th = a.th + (size_t)row * a.lay.ndim;
+    const int nc = active_components(a.lay, p0[a.lay.startind]);
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) {
         const double v = p0[k];
-        th[k] = movable(a, nc, k) ? clamp_keep_nan(v, a.lo[k], a.hi[k]) : v;
+        th[k] = coord_movable(a.lay, nc, k) ? clamp_keep_nan(v, a.lo[k], a.hi[k]) : v;
     }
     if (lane == 0) {
         a.scal[row] = a.lambda0;
@@ -58,30 +44,30 @@ __global__ __launch_bounds__(kFitWave) void mcalf_fit_start_kernel(const FitArgs
 // pixel of such a row: its logL is a finite 0 that says nothing).
 __global__ __launch_bounds__(kFitWave) void mcalf_fit_started_kernel(const FitArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    const double* p0 = a.P0 + (size_t)row * a.ndim;
-    double* th = a.th + (size_t)row * a.ndim;
-    const int nc = active_count(a, p0);
+    const double* p0 = a.P0 + (size_t)row * a.lay.ndim;
+    double* th = a.th + (size_t)row * a.lay.ndim;
+    const int nc = active_components(a.lay, p0[a.lay.startind]);
     int nan = 0;
-    for (int k = lane; k < a.ndim; k += kFitWave) nan |= (movable(a, nc, k) && isnan(p0[k])) ? 1 : 0;
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) nan |= (coord_movable(a.lay, nc, k) && isnan(p0[k])) ? 1 : 0;
     if (isfinite(a.L[row]) && !__any(nan)) return;
-    for (int k = lane; k < a.ndim; k += kFitWave) th[k] = p0[k];
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) th[k] = p0[k];
     if (lane == 0) a.status[row] = kFitBadStart;
 }
 
 __global__ __launch_bounds__(kFitWave) void mcalf_fit_begin_kernel(const FitArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    const size_t o = (size_t)row * a.ndim;
+    const size_t o = (size_t)row * a.lay.ndim;
     double* V = a.V + o;
     if (__builtin_amdgcn_readfirstlane(a.status[row]) != kFitLive) {
-        for (int k = lane; k < a.ndim; k += kFitWave) V[k] = 0.0;
+        for (int k = lane; k < a.lay.ndim; k += kFitWave) V[k] = 0.0;
         return;
     }
     const double *th = a.th + o, *G = a.G + o;
-    const int nc = active_count(a, th);
+    const int nc = active_components(a.lay, th[a.lay.startind]);
     double part = 0.0;
-    for (int k = lane; k < a.ndim; k += kFitWave) {
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) {
         const double lo = a.lo[k], hi = a.hi[k], s = hi - lo, t = th[k], g = G[k];
-        const bool pinned = !movable(a, nc, k) || !(s > 0.0) || (t <= lo && g < 0.0) || (t >= hi && g > 0.0);
+        const bool pinned = !coord_movable(a.lay, nc, k) || !(s > 0.0) || (t <= lo && g < 0.0) || (t >= hi && g > 0.0);
         const double gk = pinned ? 0.0 : s * g;
         a.pin[o + k] = pinned ? 1 : 0;
         a.gu[o + k] = gk;
@@ -108,11 +94,11 @@ __global__ __launch_bounds__(kFitWave) void mcalf_fit_begin_kernel(const FitArgs
 __global__ __launch_bounds__(kFitWave) void mcalf_fit_cg_kernel(const FitArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
     if (__builtin_amdgcn_readfirstlane(a.status[row]) != kFitLive || __builtin_amdgcn_readfirstlane(a.frozen[row])) return;
-    const size_t o = (size_t)row * a.ndim;
+    const size_t o = (size_t)row * a.lay.ndim;
     const double lam = a.scal[row], rr = a.scal[(size_t)a.nrows + row], gg = a.scal[2 * (size_t)a.nrows + row];
     double* Ap = a.T + o;
     double part = 0.0;
-    for (int k = lane; k < a.ndim; k += kFitWave) {
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) {
         const double pk = a.p[o + k];
         const double ap = a.pin[o + k] ? 0.0 : (a.hi[k] - a.lo[k]) * a.FV[o + k] + lam * pk;
         Ap[k] = ap;
@@ -125,7 +111,7 @@ __global__ __launch_bounds__(kFitWave) void mcalf_fit_cg_kernel(const FitArgs a)
     }
     const double alpha = rr / pAp;
     part = 0.0;
-    for (int k = lane; k < a.ndim; k += kFitWave) {
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) {
         a.x[o + k] += alpha * a.p[o + k];
         const double rk = a.r[o + k] - alpha * Ap[k];
         a.r[o + k] = rk;
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(kFitWave) void mcalf_fit_cg_kernel(const FitArgs a)
         return;
     }
     const double beta = rrn / rr;
-    for (int k = lane; k < a.ndim; k += kFitWave) {
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) {
         const double pk = a.r[o + k] + beta * a.p[o + k];
         a.p[o + k] = pk;
         a.V[o + k] = a.pin[o + k] ? 0.0 : (a.hi[k] - a.lo[k]) * pk;
@@ -147,9 +133,9 @@ __global__ __launch_bounds__(kFitWave) void mcalf_fit_cg_kernel(const FitArgs a)
 
 __global__ __launch_bounds__(kFitWave) void mcalf_fit_trial_kernel(const FitArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    const size_t o = (size_t)row * a.ndim;
+    const size_t o = (size_t)row * a.lay.ndim;
     const bool live = __builtin_amdgcn_readfirstlane(a.status[row]) == kFitLive;
-    for (int k = lane; k < a.ndim; k += kFitWave) {
+    for (int k = lane; k < a.lay.ndim; k += kFitWave) {
         const double t = a.th[o + k];
         double v = t;
         if (live && !a.pin[o + k]) v = clamp_keep_nan(t + (a.hi[k] - a.lo[k]) * a.x[o + k], a.lo[k], a.hi[k]);
@@ -160,12 +146,12 @@ __global__ __launch_bounds__(kFitWave) void mcalf_fit_trial_kernel(const FitArgs
 __global__ __launch_bounds__(kFitWave) void mcalf_fit_accept_kernel(const FitArgs a) {
     const int row = blockIdx.x, lane = threadIdx.x;
     if (__builtin_amdgcn_readfirstlane(a.status[row]) != kFitLive) return;
-    const size_t o = (size_t)row * a.ndim;
+    const size_t o = (size_t)row * a.lay.ndim;
     const double l0 = a.L[row], l1 = a.scal[3 * (size_t)a.nrows + row], lam = a.scal[row];
     int st = kFitLive;
     double lamn;
     if (isfinite(l1) && l1 > l0) {
-        for (int k = lane; k < a.ndim; k += kFitWave) {
+        for (int k = lane; k < a.lay.ndim; k += kFitWave) {
             a.th[o + k] = a.T[o + k];
             a.G[o + k] = a.GT[o + k];
         }

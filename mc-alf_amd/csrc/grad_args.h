@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "kernel_args.h"
+#include "theta_row.h"
 
 namespace mcalf {
 
@@ -24,9 +25,9 @@ struct GradArgs {
     double *rows, *recs, *taps, *dtaps;      // per-row workspaces: [nrows, kGradRow], [nrows, nslots, kGradRec], [nrows, tapcap] x 2
     double *F, *q;            // [nrows, npix]: transmitted flux (then g = -F cont L^T q), weighted residual
     double* part;             // [nrows, ntiles, ndim] per-tile partial sums of the gradient
-    int nrows, npix, ndim, ntiles, tapcap, nslots;
-    int nlines, ncompmax, nfill, startind, endind, freespecres, freecont, jax, jax_half, n_cap;
-    double specres_fixed, contval_fixed, velstep;
+    int nrows, npix, ntiles, tapcap, nslots, jax_half, n_cap;
+    double velstep;
+    RowLayout lay;            // how a row of P is read (theta_row.h)
     // The JVP and the HVP keep T = dF in `q`; the VJP points `q` at the caller's cotangent rows, which no kernel of its pass writes.
     const double* V;          // JVP, HVP: tangent rows of this pass [nrows, ndim]
     double* dM;               // JVP: directional derivative of the model [nrows, npix]

@@ -105,10 +105,10 @@ __device__ __forceinline__ Lsf lsf_forward(const GradArgs& a, const RowInfo& ri,
         }
     };
     const int h = ri.n;
-    if (a.jax ? (i < h || i >= a.npix - h) : h == 0) {                         // :677-681 edge reset; R <= velstep: no convolution (:445)
+    if (a.lay.jax ? (i < h || i >= a.npix - h) : h == 0) {                         // :677-681 edge reset; R <= velstep: no convolution (:445)
         s.cF = F[i];
         if (kWhat & kLsfT) s.cT = T[i];
-    } else if (a.jax) {
+    } else if (a.lay.jax) {
         for (int k = 0; k <= 2 * h; ++k) tap(k, i + k - h);
     } else {
         int j = (int)(((long)i - h) % a.npix);
@@ -139,11 +139,11 @@ __device__ __forceinline__ LsfT lsf_transposed(const GradArgs& a, const RowInfo&
         }
     };
     const int h = ri.n;
-    if (a.jax ? (i < h || i >= a.npix - h) : h == 0) {                         // an edge pixel is its own output; no taps
+    if (a.lay.jax ? (i < h || i >= a.npix - h) : h == 0) {                         // an edge pixel is its own output; no taps
         s.lq = q[i];
         if (kTan) s.ldq = dq[i];
     }
-    if (a.jax) {
+    if (a.lay.jax) {
         // interior outputs o = i - k + h with tap k read pixel i
         const int klo = max(0, i + 2 * h - a.npix + 1), khi = min(2 * h, i);
         for (int k = klo; k <= khi; ++k) tap(k, i - k + h);
@@ -164,16 +164,16 @@ __device__ __forceinline__ const double* rec_of(const GradArgs& a, int r, int sl
     return a.recs + ((size_t)r * a.nslots + slot) * kGradRec;
 }
 
-// Component c of a row's ri.nc + a.nfill: the active targets, then the fillers.  Its records are slots [slot0, slot0 + nl) of
+// Component c of a row's ri.nc + a.lay.nfill: the active targets, then the fillers.  Its records are slots [slot0, slot0 + nl) of
 // the record list (the ncompmax * nlines target slots, then the nfill filler slots); its (N, z, b) are columns [col, col + 3).
 struct Comp { int slot0, nl, col; };
 
 __device__ __forceinline__ Comp comp_of(const GradArgs& a, const RowInfo& ri, int c) {
     const bool fill = c >= ri.nc;
     Comp o;
-    o.slot0 = fill ? a.ncompmax * a.nlines + (c - ri.nc) : c * a.nlines;
-    o.nl = fill ? 1 : a.nlines;
-    o.col = fill ? a.endind + 3 * (c - ri.nc) : 1 + 3 * c + a.startind;
+    o.slot0 = fill ? a.lay.ncompmax * a.lay.nlines + (c - ri.nc) : c * a.lay.nlines;
+    o.nl = fill ? 1 : a.lay.nlines;
+    o.col = fill ? filler_col(a.lay, c - ri.nc) : target_col(a.lay, c);
     return o;
 }
 
@@ -196,14 +196,14 @@ __device__ __forceinline__ LineSums line_sums(const GradArgs& a, int r, const Co
 
 // Inactive components: exactly 0 (one thread of the tile).
 __device__ __forceinline__ void zero_inactive(const GradArgs& a, const RowInfo& ri, double* out) {
-    for (int c = ri.nc; c < a.ncompmax; ++c) {
-        const int col = 1 + 3 * c + a.startind;
+    for (int c = ri.nc; c < a.lay.ncompmax; ++c) {
+        const int col = target_col(a.lay, c);
         out[col] = out[col + 1] = out[col + 2] = 0.0;
     }
 }
 
 __device__ __forceinline__ double* part_of(const GradArgs& a, int r) {
-    return a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.ndim;
+    return a.part + ((size_t)r * a.ntiles + blockIdx.x) * a.lay.ndim;
 }
 
 // A tile's continuum and R partials summed over its pixels, and the ncomp cell.  has_R false: the R cell is exactly 0.
@@ -212,15 +212,15 @@ __device__ __forceinline__ void reduce_cont_R(const GradArgs& a, int r, double p
     pR = block_sum(pR, lds);
     if (threadIdx.x == 0) {
         double* out = part_of(a, r);
-        if (a.freespecres) out[0] = has_R ? pR : 0.0;
-        if (a.freecont) out[a.freespecres ? 1 : 0] = pc;
-        out[a.startind] = 0.0;                                                     // the ncomp slot
+        if (a.lay.freespecres) out[0] = has_R ? pR : 0.0;
+        if (a.lay.freecont) out[cont_col(a.lay)] = pc;
+        out[a.lay.startind] = 0.0;                                                 // the ncomp slot
     }
 }
 
 // ---- tap moments ----
 
-__device__ __forceinline__ bool no_taps(const GradArgs& a, int n) { return !a.jax && n == 0; }
+__device__ __forceinline__ bool no_taps(const GradArgs& a, int n) { return !a.lay.jax && n == 0; }
 
 // sum_k w_k (k - n)^2 over the 2n + 1 taps (each thread reads the taps it wrote itself); every thread gets it.
 __device__ __forceinline__ double tap_m2(const double* taps, int n, double* lds) {
@@ -243,46 +243,38 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_setup_kernel(const Grad
     __shared__ double lds[kGradBlock];
     const int r = blockIdx.x;
     const int t = threadIdx.x;
-    const double* p = a.P + (size_t)r * a.ndim;
-    const double R = a.freespecres ? p[0] : a.specres_fixed;                      // hires_fitter.py:412-417 / :572
-    const double cont = a.freecont ? p[a.freespecres ? 1 : 0] : a.contval_fixed;  // :419-425 / :571
-    const double ncv = p[a.startind];
-    const double nct = a.jax ? floor(ncv) : trunc(ncv);                          // :428 int() / :616 floor
-    const int nc = (nct >= 1.0) ? ((nct >= (double)a.ncompmax) ? a.ncompmax : (int)nct) : 0;
+    const double* p = a.P + (size_t)r * a.lay.ndim;
+    const double R = row_resolution(a.lay, p), cont = row_continuum(a.lay, p);
+    const int nc = active_components(a.lay, p[a.lay.startind]);
 
+    const int ntarget = a.lay.ncompmax * a.lay.nlines;
     for (int slot = t; slot < a.nslots; slot += kGradBlock) {
         int q;
         const LineDev* ln;
-        if (slot < a.ncompmax * a.nlines) {
-            const int c = slot / a.nlines;
-            q = 1 + 3 * c + a.startind;                                            // :431 (N, z, b)
-            ln = a.lines + (slot - c * a.nlines);
+        if (slot < ntarget) {
+            const int c = slot / a.lay.nlines;
+            q = target_col(a.lay, c);
+            ln = a.lines + (slot - c * a.lay.nlines);
         } else {
-            q = 3 * (slot - a.ncompmax * a.nlines) + a.endind;                     // :439
-            ln = a.lines + a.nlines;
+            q = filler_col(a.lay, slot - ntarget);
+            ln = a.lines + a.lay.nlines;
         }
         const double logN = p[q], z = p[q + 1], b = p[q + 2];
-        const double rdnu = ln->wrest_cm / (b * 1e5);                              // 1/dnu (:360, :376)
+        const LineScale s = line_scale(z, b, *ln, pow(10.0, logN));
         double* rec = a.recs + ((size_t)r * a.nslots + slot) * kGradRec;
-        rec[0] = (z + 1.0) * rdnu;                                                 // u = nu A - B  (:362)
-        rec[1] = ln->nujk * rdnu;
-        rec[2] = ln->gamma4pi * rdnu;                                              // a (:361)
-        rec[3] = kTauConst * pow(10.0, logN) * ln->f * rdnu;                       // K = cne / dnu (:364-365)
-        rec[4] = rdnu;
+        rec[0] = s.A;                                                              // u = nu A - B
+        rec[1] = s.B;
+        rec[2] = s.a;
+        rec[3] = s.K;
+        rec[4] = s.rdnu;
         rec[5] = 1.0 / b;
     }
 
     // taps: the numpy path's astropy count (none when R <= velstep), the JAX path's fixed grid
     const double sigma = (R / kFwhmToSigma) / a.velstep;
-    int n = 0;
-    bool bad = false;
-    if (a.jax) {
-        n = a.jax_half;
-    } else if (R > a.velstep) {
-        const double nd = ceil(kKernelReach * sigma);                               // :458
-        if (!(nd <= (double)a.n_cap)) bad = true;
-        else n = (int)nd;
-    }
+    const LsfWidth lw = lsf_half_width(R, a.velstep, a.lay.jax, a.jax_half, a.n_cap);
+    const int n = lw.n;
+    const bool bad = lw.bad;
     double* taps = a.taps + (size_t)r * a.tapcap;
     double* dtaps = a.dtaps + (size_t)r * a.tapcap;
     const double inv2s2 = 0.5 / (sigma * sigma);
@@ -307,7 +299,7 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_setup_kernel(const Grad
     const double bot = block_sum(bs, lds);                                         // astropy divides by the tap sum (1 to rounding)
     if (t == 0) {
         double* w = a.rows + (size_t)r * kGradRow;
-        w[0] = R; w[1] = cont; w[2] = (double)n; w[3] = (double)nc; w[4] = bad ? 1.0 : 0.0; w[5] = a.jax ? 1.0 : bot;
+        w[0] = R; w[1] = cont; w[2] = (double)n; w[3] = (double)nc; w[4] = bad ? 1.0 : 0.0; w[5] = a.lay.jax ? 1.0 : bot;
         w[6] = w[7] = 0.0;
     }
 }
@@ -321,7 +313,7 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_forward_kernel(const Gr
     const RowInfo ri = row_info(a, r);
     const double nu = a.nu[i];
     double tau = 0.0;
-    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+    for (int c = 0; c < ri.nc + a.lay.nfill; ++c) {
         const Comp k = comp_of(a, ri, c);
         for (int l = 0; l < k.nl; ++l) {
             const double* rec = rec_of(a, r, k.slot0 + l);
@@ -387,7 +379,7 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_deriv_kernel(const Grad
     const double g = valid ? a.F[(size_t)r * a.npix + i] : 0.0;
     const double nu = valid ? a.nu[i] : a.nu[0];
     double* out = part_of(a, r);
-    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+    for (int c = 0; c < ri.nc + a.lay.nfill; ++c) {
         const Comp k = comp_of(a, ri, c);
         LineSums s = line_sums(a, r, k, nu);
         s.sN *= g * kLn10; s.sz *= g; s.sb *= g;
@@ -401,18 +393,18 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_grad_deriv_kernel(const Grad
 template <bool kVeto>
 __device__ __forceinline__ void finalize_cell(const GradArgs& a) {
     const long e = (long)blockIdx.x * kGradBlock + threadIdx.x;
-    if (e >= (long)a.nrows * a.ndim) return;
-    const int r = (int)(e / a.ndim), k = (int)(e - (long)r * a.ndim);
+    if (e >= (long)a.nrows * a.lay.ndim) return;
+    const int r = (int)(e / a.lay.ndim), k = (int)(e - (long)r * a.lay.ndim);
     const double lg = kVeto ? a.logL[r] : 0.0;
     double s;
     if (a.rows[(size_t)r * kGradRow + 4] != 0.0 || !(lg > -INFINITY)) {
         s = NAN;                                                                    // too many taps, veto (-inf) or NaN row
     } else {
         s = 0.0;
-        const double* p = a.part + (size_t)r * a.ntiles * a.ndim + k;
-        for (int t = 0; t < a.ntiles; ++t) s += p[(size_t)t * a.ndim];
+        const double* p = a.part + (size_t)r * a.ntiles * a.lay.ndim + k;
+        for (int t = 0; t < a.ntiles; ++t) s += p[(size_t)t * a.lay.ndim];
     }
-    a.G[(size_t)r * a.ndim + k] = s;
+    a.G[(size_t)r * a.lay.ndim + k] = s;
 }
 
 __global__ __launch_bounds__(kGradBlock) void mcalf_grad_finalize_kernel(const GradArgs a) { finalize_cell<true>(a); }
@@ -427,10 +419,10 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_forward_kernel(const Gra
     const int i = blockIdx.x * kGradBlock + threadIdx.x;
     if (i >= a.npix) return;
     const RowInfo ri = row_info(a, r);
-    const double* v = a.V + (size_t)r * a.ndim;
+    const double* v = a.V + (size_t)r * a.lay.ndim;
     const double nu = a.nu[i];
     double tau = 0.0, dtau = 0.0;
-    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+    for (int c = 0; c < ri.nc + a.lay.nfill; ++c) {
         const Comp k = comp_of(a, ri, c);
         const LineSums s = line_sums(a, r, k, nu);
         tau += s.sN;
@@ -452,9 +444,9 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_jvp_model_kernel(const GradA
         out[i] = NAN;
         return;
     }
-    const double* v = a.V + (size_t)r * a.ndim;
-    const double vR = a.freespecres ? v[0] : 0.0;
-    const double vc = a.freecont ? v[a.freespecres ? 1 : 0] : 0.0;
+    const double* v = a.V + (size_t)r * a.lay.ndim;
+    const double vR = a.lay.freespecres ? v[0] : 0.0;
+    const double vc = a.lay.freecont ? v[cont_col(a.lay)] : 0.0;
     const Lsf s = lsf_forward<kLsfR | kLsfT>(a, ri, r, i);
     out[i] = ri.cont * s.cT + vc * s.cF + vR * ri.cont * s.rF;
 }
@@ -475,10 +467,10 @@ namespace {
 struct RowTangent { double vR, vc; };
 
 __device__ __forceinline__ RowTangent row_tangent(const GradArgs& a, int r, const RowInfo& ri) {
-    const double* v = a.V + (size_t)r * a.ndim;
+    const double* v = a.V + (size_t)r * a.lay.ndim;
     RowTangent o;
-    o.vR = (a.freespecres && (a.jax || ri.n > 0)) ? v[0] : 0.0;
-    o.vc = a.freecont ? v[a.freespecres ? 1 : 0] : 0.0;
+    o.vR = (a.lay.freespecres && (a.lay.jax || ri.n > 0)) ? v[0] : 0.0;
+    o.vc = a.lay.freecont ? v[cont_col(a.lay)] : 0.0;
     return o;
 }
 
@@ -532,7 +524,7 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_model_kernel(const GradA
         pc = dqv * s.cF + qv * (s.cT + rt.vR * s.rF);
         pR = (dqv * ri.cont + qv * rt.vc) * s.rF + qv * ri.cont * (s.rT + rt.vR * s.rrF);
     }
-    reduce_cont_R(a, r, pc, pR, a.jax || ri.n > 0, lds);
+    reduce_cont_R(a, r, pc, pR, a.lay.jax || ri.n > 0, lds);
 }
 
 // g and dg in place of F and T from one transposed walk with all three sums.
@@ -560,9 +552,9 @@ __global__ __launch_bounds__(kGradBlock) void mcalf_hvp_deriv_kernel(const GradA
     const double g = valid ? a.F[(size_t)r * a.npix + i] : 0.0;
     const double dg = valid ? a.q[(size_t)r * a.npix + i] : 0.0;
     const double nu = valid ? a.nu[i] : a.nu[0];
-    const double* v = a.V + (size_t)r * a.ndim;
+    const double* v = a.V + (size_t)r * a.lay.ndim;
     double* out = part_of(a, r);
-    for (int c = 0; c < ri.nc + a.nfill; ++c) {
+    for (int c = 0; c < ri.nc + a.lay.nfill; ++c) {
         const Comp k = comp_of(a, ri, c);
         double tN = 0.0, tz = 0.0, tb = 0.0, tzz = 0.0, tzb = 0.0, tbb = 0.0;
         for (int l = 0; l < k.nl; ++l) {

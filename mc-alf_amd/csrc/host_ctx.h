@@ -29,6 +29,7 @@
 #include "ctx_plan.h"
 #include "grad_args.h"
 #include "prior_args.h"
+#include "theta_row.h"
 
 #define MCALF_STR_(x) #x
 #define MCALF_STR(x) MCALF_STR_(x)
@@ -525,6 +526,12 @@ inline PriorDev prior_dev(const mcalf_ctx* ctx) {
     const double* g = ctx->ngauss > 0 ? ctx->d_gauss.p : nullptr;
     const size_t n = (size_t)ctx->ndim;
     return {ctx->d_prior, ctx->d_prior + n, g, g ? g + n : nullptr, g ? g + 2 * n : nullptr, ctx->ndim};
+}
+
+// How the context's parameter rows are read, for a kernel's arguments (theta_row.h).
+inline RowLayout row_layout(const mcalf_ctx* ctx) {
+    return {ctx->ndim, ctx->nlines, ctx->ncompmax, ctx->nfill, ctx->startind, ctx->endind, ctx->freespecres, ctx->freecont,
+            ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0, ctx->specres_fixed, ctx->contval_fixed};
 }
 
 // ---- host_eqw.cpp: the equivalent-width entries -------------------------------------------------------------------------

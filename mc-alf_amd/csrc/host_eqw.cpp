@@ -52,8 +52,7 @@ int run_eqw(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, d
     EqwArgs a = {};
     a.nu = ctx->d_nu; a.dlam = ctx->d_dlam; a.lines = ctx->d_lines; a.tabs = ctx->d_tabs;
     a.recs = ctx->eb[mcalf_ctx::kEbRecs]; a.part = ctx->eb[mcalf_ctx::kEbPart];
-    a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = eqw_ntiles(ctx); a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax;
-    a.startind = ctx->startind; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0; a.indexing = indexing;
+    a.npix = (int)ctx->npix; a.ntiles = eqw_ntiles(ctx); a.indexing = indexing; a.lay = row_layout(ctx);
     const size_t nrec = (size_t)eqw_nrec(ctx), ncells = (size_t)eqw_ncells(ctx);
     for (int64_t row0 = 0; row0 < batch; row0 += chunk) {
         a.P = dP + (size_t)row0 * ctx->ndim;

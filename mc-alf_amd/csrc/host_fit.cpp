@@ -149,8 +149,7 @@ int run_fit(mcalf_ctx* ctx, const FitRows& r, int64_t batch, const mcalf_fit_opt
         a.T = fb[mcalf_ctx::kFbT]; a.G = fb[mcalf_ctx::kFbG]; a.GT = fb[mcalf_ctx::kFbGT]; a.gu = fb[mcalf_ctx::kFbGu];
         a.x = fb[mcalf_ctx::kFbX]; a.r = fb[mcalf_ctx::kFbR]; a.p = fb[mcalf_ctx::kFbPv]; a.V = fb[mcalf_ctx::kFbV]; a.FV = fb[mcalf_ctx::kFbFV];
         a.scal = fb[mcalf_ctx::kFbScal]; a.frozen = ctx->fit_int; a.pin = ctx->fit_int + rows; a.live = ctx->d_fit_live;
-        a.nrows = (int)n; a.ndim = ctx->ndim; a.npix = (int)ctx->npix; a.startind = ctx->startind; a.ncompmax = ctx->ncompmax;
-        a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0;
+        a.nrows = (int)n; a.npix = (int)ctx->npix; a.lay = row_layout(ctx);
         a.lambda0 = o.lambda0; a.ftol = o.ftol;
         double* LT = a.scal + 3 * (size_t)n;
         if ((rc = launch_fit(ctx, kFitStart, a, stream)) || (rc = run_product(ctx, kProdGrad, {a.th, nullptr, a.G, a.L}, n, stream)) ||

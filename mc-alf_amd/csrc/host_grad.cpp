@@ -50,11 +50,9 @@ GradArgs grad_args(const mcalf_ctx* ctx) {
     a.rows = gb[mcalf_ctx::kGbRows]; a.recs = gb[mcalf_ctx::kGbRecs]; a.taps = gb[mcalf_ctx::kGbTaps]; a.dtaps = gb[mcalf_ctx::kGbDtaps];
     a.F = gb[mcalf_ctx::kGbF]; a.q = gb[mcalf_ctx::kGbQ]; a.part = gb[mcalf_ctx::kGbPart];
     a.ddtaps = gb[mcalf_ctx::kGbDdtaps]; a.hq = gb[mcalf_ctx::kGbHq]; a.hdq = gb[mcalf_ctx::kGbHdq];
-    a.npix = (int)ctx->npix; a.ndim = ctx->ndim; a.ntiles = grad_ntiles(ctx); a.tapcap = grad_tapcap(ctx); a.nslots = grad_nslots(ctx);
-    a.nlines = ctx->nlines; a.ncompmax = ctx->ncompmax; a.nfill = ctx->nfill; a.startind = ctx->startind; a.endind = ctx->endind;
-    a.freespecres = ctx->freespecres; a.freecont = ctx->freecont; a.jax = ctx->conv_mode == MCALF_CONV_SAME_EDGE_JAX ? 1 : 0;
-    a.jax_half = ctx->jax_half; a.n_cap = grad_ncap(ctx);
-    a.specres_fixed = ctx->specres_fixed; a.contval_fixed = ctx->contval_fixed; a.velstep = ctx->velstep;
+    a.npix = (int)ctx->npix; a.ntiles = grad_ntiles(ctx); a.tapcap = grad_tapcap(ctx); a.nslots = grad_nslots(ctx);
+    a.jax_half = ctx->jax_half; a.n_cap = grad_ncap(ctx); a.velstep = ctx->velstep;
+    a.lay = row_layout(ctx);
     return a;
 }
 
@@ -83,7 +81,7 @@ namespace {
 dim3 grad_grid(GradKernel k, const GradArgs& a) {
     if (k < kGradFirstPixel) return dim3((unsigned)a.nrows);
     if (k < kGradFirstCell) return dim3((unsigned)a.ntiles, (unsigned)a.nrows);
-    return dim3((unsigned)(((int64_t)a.nrows * a.ndim + kGradBlock - 1) / kGradBlock));
+    return dim3((unsigned)(((int64_t)a.nrows * a.lay.ndim + kGradBlock - 1) / kGradBlock));
 }
 
 }  // namespace

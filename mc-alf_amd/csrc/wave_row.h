@@ -1,6 +1,6 @@
 // Device helpers of the kernels that give ONE wave64 to a row (fit_kernels.hip, ns_kernels.hip, ens_kernels.hip): lane k owns
 // coordinates k, k + 64, ...; a row's scalars are folded over the lanes by one fixed xor-butterfly and made wave-uniform with
-// readfirstlane; the random words of a row are Philox4x64-10 blocks.
+// readfirstlane; the random words of a row are Philox4x64-10 blocks.  (eqw_kernels.hip takes wave_sum alone, for its waves' partials.)
 // The only floating-point arithmetic in here is wave_sum's add, which has no product to contract with: it does not matter
 // whether the including file has switched contraction to FMA off (ns_kernels.hip and ens_kernels.hip do, before they include
 // this; fit_kernels.hip does not).

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""A/B of two builds of the library: every plan of the likelihood's entries once, each case in a FRESH context, each build in a
-process of its own (MCALF_HIP_LIB); outputs compared bit for bit and the whole mcalf_last_launch record field by field.
+"""A/B of two builds of the library: every plan of the likelihood's entries and every analysis entry once, each case in a FRESH
+context, each build in a process of its own (MCALF_HIP_LIB); outputs compared bit for bit and the whole mcalf_last_launch record
+field by field.
 
     python tools/ab_bits.py libA.so libB.so      # exit status 1 when anything differs
     python tools/ab_bits.py --child out.json     # the cases alone, with the library MCALF_HIP_LIB names (e.g. under a profiler)
 
 Cases: the device entry (one block, three blocks), the zero-copy small call, the streaming launch, the row-block pipeline
 (MCALF_STREAM=0), chi2, model and single-component output, the cube entry (small, streaming, staged), a wide-LSF context,
-single-tile (C, B) and tiled (E) spectra."""
+single-tile (C, B) and tiled (E) spectra; and, on a 300-pixel problem under both conv modes, with and without fillers, with
+count slots from below 0 to above ncompmax: loglike_grad, model JVP / VJP, loglike_hvp, the Fisher product, eqw in both
+indexings with and without Wblend, maximize."""
 import json
 import os
 import subprocess
@@ -99,6 +102,30 @@ def child(path):
     case("wide model", kw, lambda fit: [fit.model_batch(P[:3])])
     case("wide onecomp", kw, lambda fit: [fit.reconstruct_onecomp(8.0, 0.95, 13.5, 3.0, 20.0)])
     case("wide cube", kw, lambda fit: list(fit.loglike_cube_batch(cubes)))
+    # the analysis entries (gradient, Jacobian and Hessian products, Fisher product, equivalent widths, fit): both conv modes, with
+    # and without fillers, rows whose count slot is 0, fractional, ncompmax and above it
+    for mode in ("numpy", "jax"):
+        for nfill in (0, 2):
+            rng = np.random.default_rng(444 + nfill)
+            wl = np.linspace(6185.0, 6215.0, 302)[1:-1]
+            kw = dict(fitrange=[[6185.0, 6215.0]], fitlines=["CIV 1548", "CIV 1550"], linepars=[(1548.204, 0.1899, 2.643e8), (1550.781, 0.09475, 2.628e8)],
+                      ncomp=[0, 3], nfill=nfill, specres=[6.0, 9.0], contval=[0.9, 1.1], Nrange=[12.5, 14.5], brange=[8.0, 40.0], zrange=[2.998, 3.004],
+                      spectrum=(wl, 1 + rng.normal(0, 0.03, 300), np.full(300, 0.03)), conv_mode=mode)
+            P = workloads.draw_P(kw, 12, rng)
+            P[:, 2] = [0.0, 0.7, 1.0, 1.5, 2.0, 2.999, 3.0, 3.5, 4.2, 1e9, -0.5, -2.0]        # (startind 2: R and the continuum are free)
+            V = rng.uniform(-1.0, 1.0, P.shape) * 1e-3
+            Q = rng.normal(0.0, 1.0, (12, 300))
+            tag = "%s nfill %d " % (mode, nfill)
+            case(tag + "grad", kw, lambda fit: list(fit.loglike_grad_batch(P)))
+            case(tag + "jvp", kw, lambda fit: [fit.model_jvp_batch(P, V)])
+            case(tag + "vjp", kw, lambda fit: [fit.model_vjp_batch(P, Q)])
+            case(tag + "hvp", kw, lambda fit: [fit.loglike_hvp_batch(P, V)])
+            case(tag + "fisher", kw, lambda fit: [fit.fisher_matvec_batch(P, V)])
+            for ref in (False, True):
+                name = tag + ("eqw as written" if ref else "eqw layout")
+                case(name, kw, lambda fit: list(fit.eqw_batch(P, reference_indexing=ref)))
+                case(name + ", no blend", kw, lambda fit: [fit.eqw_batch(P, reference_indexing=ref, blend=False)[0]])
+            case(tag + "maximize", kw, lambda fit: list(fit.maximize_batch(P, max_iter=4)))
     json.dump(res, open(path, "w"))
 
 
