@@ -92,7 +92,9 @@ extern "C" {
                                     mcalf_ensemble_batch[_device], the ensemble MCMC sampler: stretch and DE moves of a walker
                                     set in the unit cube, the chain kept on the device;
                                     mcalf_tempered_batch[_device], parallel tempering of that sampler: a ladder of temperatures
-                                    moved in the same launches, swaps between neighbours) */
+                                    moved in the same launches, swaps between neighbours;
+                                    mcalf_nested_open / _advance / _finish / _read / _last_round / _close / _footprint /
+                                    _set_timing / _last_times, a nested-sampling run whose live and dead points stay on the device) */
 
 enum {
     MCALF_OK = 0,
@@ -679,6 +681,97 @@ int mcalf_tempered_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, con
 int mcalf_tempered_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const double* beta, const mcalf_pt_opts* opts,
                                 double* dU, double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept, int32_t* dnswap,
                                 double* dCU, double* dCL, void* stream);
+
+/* A device-resident nested-sampling run: the live set UL [nlive][ndim] / LL [nlive] and the dead rows UD [max_dead][ndim] /
+ * LD [max_dead] stay on the device from mcalf_nested_open to mcalf_nested_close; a round transfers no rows, only one record of
+ * K + 8 words.  key(L) = L with NaN as -inf.  With K = batch, round r (r = 0, 1, ... over the whole run) is
+ *   rank     rank[i] = #{ j : key_j < key_i, or key_j == key_i and j < i }, compared as doubles (-0.0 == 0.0; ties keep index
+ *            order: numpy's stable argsort); order[rank[i]] = i.
+ *   select   dying = order[0, K) in that order; lmin = key[order[K - 1]]; r0 = rows with key <= lmin; nstarts = nlive - r0.
+ *            nstarts == 0 is a plateau: the run stops before anything dies.  Chain j starts from
+ *            pick_j = order[r0 + w0 mod nstarts], w0 the first word of the Philox4x64-10 block at counter (r + 1, 0, j, 0) and
+ *            key (seed, 3) -- numpy's Philox(counter=[r, 0, j, 0], key=[seed, 3]) returns it first.  (Key word 1: 0 the slice
+ *            step, 1 the ensemble moves, 2 the tempering swaps, 3 these picks.)  Its stream id is r K + j.
+ *   moments  mean and covariance (divisor n - 1) of the cube rows of the n = nlive - K survivors order[K, nlive), those equal to
+ *            lmin included, in two passes.  The survivors are cut into 128 contiguous chunks of ceil(n / 128) rows; a chunk's sum
+ *            runs over its rows in order, the chunk sums are added in chunk order.  One survivor: a zero covariance.
+ *   Cholesky of the covariance with 1e-9 max(mean of the variances, 1e-300) added to the diagonal; D = (factor)^T, ndim direction
+ *            rows [ndim][ndim], upper triangular.  A non-finite entry of the covariance or a pivot that is not positive:
+ *            D = diag(std), 1 where the variance is not finite and positive.
+ *   replace  mcalf_slice_replace_batch's step (above) over the K device rows U0_j = UL[pick_j], Lmin_j = lmin, sid_j, with
+ *            ndirs = ndim, as the host entry runs it: it reads the 4-byte count after every step, and honours
+ *            mcalf_set_slice_compact and a Gaussian prior (the constrained quantity and every L here are then logL + lnprior).
+ *   retire   replacements with status < 0 or not (L > lmin) are counted.  At zero the dying rows (U, L) go to the dead slots
+ *            ndead + 0 .. K - 1 in death order and the replacements into the live rows they leave.  Otherwise the call ends with
+ *            MCALF_ERR_INVALID naming the first such row, the live and the dead set as they were before the round.
+ * Integer results only in rank and select, no floating-point atomics anywhere: a round's bits depend on the live set, r and the
+ * options alone -- not on how the rounds are cut into calls, on the packing or on the device count.  The evidence is nested.py's:
+ * point j of a round dies at live count nlive - j, ln X dropping by 1 / (nlive - j), ln w = ln X + ln(-expm1(-1 / n)) + key; after
+ * the last round the remaining live points die in key order at counts nlive .. 1; ln Z is one left fold of logaddexp over all
+ * weights, H = sum p (key - ln Z), logZ_err = sqrt(max(H, 0) / nlive).  nlive <= 262144 (the rank is counted: nlive^2 comparisons
+ * a round) and ndim <= 256, MCALF_ERR_RANGE otherwise.  A multi-device context runs the whole run on its first device entry: bit
+ * for bit a single-device context's.  A context holds one run at a time. */
+typedef struct {
+    int32_t batch;           /* K: rows replaced per round, 1 <= K < nlive */
+    int32_t nmoves;          /* slice moves per replacement chain, >= 0 */
+    int32_t max_steps;       /* lock steps of a round's replacement call, >= 0 */
+    int32_t reserved;
+    uint64_t seed;           /* the Philox key word 0 of the picks and of the slice step */
+    double dlogz;            /* the stop test's tolerance, >= 0 (0: never stops) */
+    int64_t max_dead;        /* dead rows the device keeps, >= nlive + K (rounds K + nlive are needed for a run of `rounds`) */
+} mcalf_nested_opts;         /* 40 bytes */
+enum { MCALF_NESTED_BUDGET = 0, MCALF_NESTED_CONVERGED = 1, MCALF_NESTED_PLATEAU = 2, MCALF_NESTED_FULL = 3 };
+typedef struct {
+    int64_t nlive, ndead;    /* live rows; dead rows so far */
+    int64_t rounds;          /* rounds completed over the whole run */
+    int64_t nevals;          /* likelihood evaluations: the initial points and every trial of every chain */
+    int64_t unfinished;      /* replacements that came back with status 0 (kept: they satisfy their constraint) */
+    int64_t rows_launched;   /* rows handed to likelihood launches, the initial nlive included */
+    double logX, logZ;       /* ln X and the running ln Z (it steers the stop; mcalf_nested_finish makes the final one) */
+    double max_key;          /* the largest live key */
+    int32_t reason;          /* why the last mcalf_nested_advance returned: MCALF_NESTED_* */
+    int32_t reserved;
+} mcalf_nested_state_t;      /* 80 bytes */
+/* Opens a run from the host rows U0 [nlive][ndim] of the unit cube: allocates the state (buffers a context already holds from an
+ * earlier run of the same or a larger size are reused: nothing is allocated then) and evaluates the initial points by one
+ * replacement call with Lmin = -inf and nmoves = 0 -- logL (+ lnprior under a Gaussian prior).  A row that call refuses (a NaN or
+ * an entry outside the cube: no prior mass) takes logL = -inf unless its logL is NaN; with the rows of NaN or -inf logL it sorts
+ * first and carries no weight.  Refused before any device work, naming the
+ * argument (MCALF_ERR_INVALID): ctx, U0 or opts NULL; no prior set; batch outside [1, nlive); nmoves < 0; max_steps < 0; dlogz
+ * negative or NaN; max_dead < nlive + batch; a run already open.  MCALF_ERR_RANGE: nlive above 262144 or ndim above 256 (the
+ * message names the cap); a state above 4 GiB (the message names the largest max_dead). */
+int mcalf_nested_open(mcalf_ctx* ctx, const double* U0, int64_t nlive, const mcalf_nested_opts* opts);
+/* Runs rounds until the stop test max key + ln X < ln dlogz + ln Z holds before a round (reason 1), a round finds a plateau
+ * (2), the dead rows cannot take another round plus the final nlive (3: ndead + K + nlive > max_dead), or max_rounds rounds of
+ * this call have run (0) -- tested in that order.  out (NULL: not wanted) takes the state.  Calls continue each other: a round's
+ * bits do not depend on how the rounds were cut into calls.  MCALF_ERR_INVALID: ctx NULL, max_rounds < 0, no open run, a
+ * finished run, a replacement outside its constraint. */
+int mcalf_nested_advance(mcalf_ctx* ctx, int32_t max_rounds, mcalf_nested_state_t* out);
+/* Retires the remaining live points in key order (ndead grows by nlive), reads the dead logL once (one device-to-host copy of
+ * LD) and computes ln Z, sqrt(max(H, 0) / nlive) and H (each pointer NULL: not wanted); the normalised log weights are kept for
+ * mcalf_nested_read.  Afterwards the run only reads and closes.  MCALF_ERR_INVALID: ctx NULL, no open run, a finished run. */
+int mcalf_nested_finish(mcalf_ctx* ctx, double* logZ, double* logZ_err, double* H);
+/* Dead rows [first, first + count) in death order into the host arrays cube, theta [count][ndim], logL, logw [count]; any of
+ * them NULL: not wanted.  theta is made on the fly by mcalf_scale_cube_batch's kernel (never stored).  MCALF_ERR_INVALID: ctx
+ * NULL, no run, a range outside [0, ndead], logw before mcalf_nested_finish. */
+int mcalf_nested_read(mcalf_ctx* ctx, int64_t first, int64_t count, double* cube, double* theta, double* logL, double* logw);
+/* What the last round selected (a plateau round included), for tests and diagnostics: dying, pick [K], D [ndim][ndim], lmin
+ * [1]; any NULL: not wanted.  MCALF_ERR_INVALID: ctx NULL, no run, no round yet. */
+int mcalf_nested_last_round(mcalf_ctx* ctx, int32_t* dying, int32_t* pick, double* D, double* lmin);
+/* Ends the run (finished or not); its device buffers stay with the context for the next run and are released by mcalf_destroy.
+ * Without a run it does nothing.  ctx NULL: MCALF_ERR_INVALID. */
+int mcalf_nested_close(mcalf_ctx* ctx);
+/* Device bytes the context holds for its runs (the live and dead rows of the largest run so far and the rounds' workspaces;
+ * 0 before the first mcalf_nested_open).  The dead rows dominate: max_dead (ndim + 1) 8 bytes.  It grows only when a run needs a
+ * larger buffer than any before it: a value that does not change over a run says that the run allocated nothing.  ctx or
+ * device_bytes NULL: MCALF_ERR_INVALID. */
+int mcalf_nested_footprint(const mcalf_ctx* ctx, int64_t* device_bytes);
+/* Per-kernel times of a round, for tools: with on = 1 every following round records HIP events around its book-keeping kernels
+ * (0, the default: none; mcalf_nested_close turns it off again, so it is set on an open run).  mcalf_nested_last_times: milliseconds of the last round's rank, select, moments (both passes),
+ * Cholesky, gather, replacement call and retire into ms [7].  MCALF_ERR_INVALID: ctx or ms NULL, on outside {0, 1}, no run, the
+ * last round was not timed. */
+int mcalf_nested_set_timing(mcalf_ctx* ctx, int32_t on);
+int mcalf_nested_last_times(mcalf_ctx* ctx, double* ms);
 
 /* What the LAST call of this context actually did (tests and benchmarks assert on the path taken instead of
  * inferring it from batch sizes).  `path`: which entry plan ran; the remaining fields describe the last fused-kernel

@@ -11,6 +11,7 @@ from . import broker  # noqa: F401
 from . import dist  # noqa: F401
 from . import ensemble  # noqa: F401
 from . import nested  # noqa: F401
+from . import nested_device  # noqa: F401
 from . import routines  # noqa: F401
 from . import tempering  # noqa: F401
 from . import workloads  # noqa: F401

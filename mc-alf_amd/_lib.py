@@ -174,6 +174,37 @@ class mcalf_pt_opts(C.Structure):
     ]
 
 
+class mcalf_nested_opts(C.Structure):
+    _fields_ = [
+        ("batch", C.c_int32),
+        ("nmoves", C.c_int32),
+        ("max_steps", C.c_int32),
+        ("reserved", C.c_int32),
+        ("seed", C.c_uint64),
+        ("dlogz", C.c_double),
+        ("max_dead", C.c_int64),
+    ]
+
+
+class mcalf_nested_state_t(C.Structure):
+    _fields_ = [
+        ("nlive", C.c_int64),
+        ("ndead", C.c_int64),
+        ("rounds", C.c_int64),
+        ("nevals", C.c_int64),
+        ("unfinished", C.c_int64),
+        ("rows_launched", C.c_int64),
+        ("logX", C.c_double),
+        ("logZ", C.c_double),
+        ("max_key", C.c_double),
+        ("reason", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+# why mcalf_nested_advance returned
+MCALF_NESTED_BUDGET, MCALF_NESTED_CONVERGED, MCALF_NESTED_PLATEAU, MCALF_NESTED_FULL = 0, 1, 2, 3
+
 # the largest ladder of mcalf_tempered_batch
 MCALF_PT_MAX_TEMPS = 64
 
@@ -231,6 +262,15 @@ SYMBOLS = {
     "mcalf_ensemble_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_tempered_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_tempered_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_nested_open": (C.c_int, [_CTX, _P, C.c_int64, _P]),
+    "mcalf_nested_advance": (C.c_int, [_CTX, C.c_int32, _P]),
+    "mcalf_nested_finish": (C.c_int, [_CTX, _P, _P, _P]),
+    "mcalf_nested_read": (C.c_int, [_CTX, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "mcalf_nested_last_round": (C.c_int, [_CTX, _P, _P, _P, _P]),
+    "mcalf_nested_close": (C.c_int, [_CTX]),
+    "mcalf_nested_footprint": (C.c_int, [_CTX, C.POINTER(C.c_int64)]),
+    "mcalf_nested_set_timing": (C.c_int, [_CTX, C.c_int32]),
+    "mcalf_nested_last_times": (C.c_int, [_CTX, _P]),
     "mcalf_model_jvp_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),
     "mcalf_model_jvp_batch_device": (C.c_int, [_CTX, _P, _P, C.c_int64, _P, _P]),
     "mcalf_model_vjp_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),

@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_nsrun.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.  What a context
 // decides from its spec alone -- the checks, the launch geometry, the host tables -- is ctx_plan.h (no HIP there: the CPU tests
@@ -28,6 +28,7 @@
 #include "kernel_args.h"
 #include "ctx_plan.h"
 #include "grad_args.h"
+#include "ns_evidence.h"
 #include "prior_args.h"
 #include "theta_row.h"
 
@@ -156,6 +157,37 @@ struct DevBuf {
     T* operator->() const { return p; }
 };
 template <typename T> using PinBuf = DevBuf<T, true>;
+
+// A device-resident nested-sampling run (host_nsrun.cpp: mcalf_nested_*).  The buffers are grown by mcalf_nested_open and stay
+// with the context when a run is closed, as every workspace does: a second run of the same or a smaller size allocates nothing.
+struct NsRun {
+    enum Phase { kClosed, kOpen, kFinished };
+    Phase phase = kClosed;
+    mcalf_nested_opts opts = {};
+    int64_t nlive = 0, ndead = 0, rounds = 0, nevals = 0, unfinished = 0, rows_launched = 0;
+    double max_key = 0.0;                   // the largest live key, from the last round's record
+    int32_t reason = 0;                     // why the last mcalf_nested_advance returned
+    bool have_last = false;                 // a round has selected: mcalf_nested_last_round has something to report
+    bool timing = false, timed = false;     // mcalf_nested_set_timing; the last round was timed
+    NsEvidence ev;                          // ln X and the running ln Z
+    double logZ = 0.0, H = 0.0;             // mcalf_nested_finish's
+    std::vector<double> logw, host_l;       // the normalised log weights and the dead logL they were made from
+    std::vector<double> keys;               // the dead keys of a round's record, as doubles
+    DevBuf<double> UL, LL, UD, LD, meanpart, covpart, tri, var, D, U0, Lmin, Un, Ln, theta;
+    DevBuf<int32_t> rank, order, dying, pick, status, nevals_row, moves;
+    DevBuf<uint64_t> sid, rec;
+    PinBuf<uint64_t> h_rec;
+    hipEvent_t ev_t[8] = {};                // around the book-keeping kernels of a timed round
+    float last_ms[7] = {};                  // rank, select, moments, Cholesky, gather, replace, retire
+    // Device bytes the run's buffers hold (mcalf_nested_footprint).
+    size_t device_bytes() const {
+        size_t d = 0, i = 0;
+        for (const DevBuf<double>* b : {&UL, &LL, &UD, &LD, &meanpart, &covpart, &tri, &var, &D, &U0, &Lmin, &Un, &Ln, &theta}) d += b->cap;
+        for (const DevBuf<int32_t>* b : {&rank, &order, &dying, &pick, &status, &nevals_row, &moves}) i += b->cap;
+        return d * sizeof(double) + i * sizeof(int32_t) + (sid.cap + rec.cap) * sizeof(uint64_t);
+    }
+    ~NsRun() { for (hipEvent_t e : ev_t) if (e) (void)hipEventDestroy(e); }
+};
 
 struct mcalf_ctx : CtxShape {               // (the problem and geometry fields: ctx_plan.h)
     HostTrace htrace;
@@ -314,6 +346,7 @@ struct mcalf_ctx : CtxShape {               // (the problem and geometry fields:
     hipEvent_t ev_ns = nullptr;
     int ns_compact = 0;                     // MCALF_NS_COMPACT / mcalf_set_slice_compact
     mcalf_slice_stats_t ns_stats = {};
+    NsRun nsrun;                            // the device-resident run of mcalf_nested_* (a multi-device parent: its first entry's)
     // The ensemble sampler (host_ens.cpp), grown on demand.  The trial rows [T m][ndim] of the moving halves of its T temperatures
     // (mcalf_ensemble_batch: one), their logL [T m], the Hastings term and ln zeta [2][T m] and the inside flags [T m] of one half-step.  The chain is NOT among them: the host entry
     // releases it before it returns, the device entry is handed the caller's.
@@ -347,6 +380,16 @@ template <typename T> inline int grow(mcalf_ctx* ctx, DevBuf<T>& buf, size_t nee
     if (buf.p) HIP_TRY(ctx, hipFree(buf.p));
     buf.p = nullptr; buf.cap = 0;
     HIP_TRY(ctx, hipMalloc((void**)&buf.p, need_elems * sizeof(T)));
+    buf.cap = need_elems;
+    return MCALF_OK;
+}
+
+// The same for a page-locked host block.
+template <typename T> inline int grow(mcalf_ctx* ctx, PinBuf<T>& buf, size_t need_elems) {
+    if (need_elems <= buf.cap) return MCALF_OK;
+    if (buf.p) HIP_TRY(ctx, hipHostFree((void*)buf.p));
+    buf.p = nullptr; buf.cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&buf.p, need_elems * sizeof(T), hipHostMallocDefault));
     buf.cap = need_elems;
     return MCALF_OK;
 }
@@ -519,6 +562,15 @@ struct Product {
 };
 extern const Product kProdGrad, kProdJvp, kProdVjp, kProdHvp;
 int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStream_t stream);   // product `p` over device rows, on `stream`
+
+// ---- host_ns.cpp: the replacement step, for host_nsrun.cpp ---------------------------------------------------------------
+// The device rows of one call of the replacement primitive.
+struct NsRows {
+    const double *U0, *Lmin, *D; const uint64_t* sid;
+    double *U, *theta, *logL; int32_t *status, *nevals, *moves;
+};
+// The call over `batch` device rows on `stream`; poll: the host reads the count of live rows after every step and stops at 0.
+int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o, hipStream_t stream, bool poll);
 
 // ---- host_prior.cpp: the Gaussian prior -----------------------------------------------------------------------------------
 // The prior block of a (single-device) context whose box is set, for a kernel's arguments; mu is NULL when no Gaussian is set.

@@ -11,11 +11,6 @@
 
 namespace {
 
-struct NsRows {
-    const double *U0, *Lmin, *D; const uint64_t* sid;
-    double *U, *theta, *logL; int32_t *status, *nevals, *moves;
-};
-
 // Everything that is wrong with a call before any device work; `name` is the entry that reports it.  host_d: D is a host array
 // whose entries are read here.
 int ns_check(mcalf_ctx* ctx, const char* name, const NsRows& r, int64_t batch, const mcalf_slice_opts* o, bool host_d) {
@@ -78,7 +73,9 @@ int compact_steps(mcalf_ctx* ctx, NsArgs& a, const mcalf_slice_opts& o, hipStrea
 // The call over `batch` device rows on `stream`.  poll: after every step the host reads the counter of rows that proposed a
 // trial (4 bytes, through a page-locked word) and leaves the loop at 0 -- finished rows are carried, so the rows' bits are those
 // of the unconditional max_steps steps the device entry runs.  A polling call of a context with ns_compact set packs its trial
-// rows (compact_steps); the rows' bits are the same again.
+// rows (compact_steps); the rows' bits are the same again.  (Declared in host_ctx.h: host_nsrun.cpp's rounds call it too.)
+}  // namespace
+
 int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opts& o, hipStream_t stream, bool poll) {
     if (batch <= 0) return MCALF_OK;
     if (batch > 0x7fff0000LL) return set_err(ctx, MCALF_ERR_RANGE, "batch %lld too large", (long long)batch);
@@ -132,6 +129,8 @@ int run_ns(mcalf_ctx* ctx, const NsRows& r, int64_t batch, const mcalf_slice_opt
     if (r.theta) return cube_to_theta(ctx, r.U, r.theta, batch, stream);      // the transformed rows of the points
     return MCALF_OK;
 }
+
+namespace {
 
 // The host entry's device driver (host_staged.cpp: run_staged); columns in the order of NsCol.
 enum NsCol { kColU0, kColLmin, kColD, kColSid, kColU, kColTheta, kColL, kColStatus, kColNevals, kColMoves, kNsCols };
