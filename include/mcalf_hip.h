@@ -404,6 +404,42 @@ int mcalf_eqw_batch(mcalf_ctx* ctx, const double* P, int64_t batch, int32_t inde
 int mcalf_eqw_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, int32_t indexing, double* dWcomp, double* dWblend,
                            void* stream);
 
+/* Optical-depth kinematics of every row and target line, on the device (the analysis pass over a chain): WHERE in wavelength
+ * the model's absorption sits -- the integral of tau, its centroid, its width, and the wavelengths below which given fractions
+ * of it lie (q = 0.05 and 0.95 bound the Delta v90 interval of Prochaska & Wolfe 1997).  Taken on the model's tau, not on a
+ * flux, so a saturated core does not spoil them.  P is batch x ndim.  For row i and line l, with nc the row's active count as
+ * MCALF_EQW_LAYOUT reads it, slot c < nc reading (N, z, b) at startind + 1 + 3c, and dlam as mcalf_eqw_batch has it:
+ *   tau[k]   = sum_{c < nc} tau_cl(wl[k])       the slots in slot order into one accumulator that starts at 0.0; tau_cl is
+ *                                               mcalf_eqw_batch's (the folded tables, K hjert_general, nothing for |1 + z| > 1e100)
+ *   t[k]     = tau[k] dlam[k]
+ *   S[k]     = sum_{j <= k} t[j],   I = S[npix - 1]                  integral of tau dlambda, Angstrom, observed frame
+ *   piv      = wl[npix / 2],   M1 = sum t[k] (wl[k] - piv),   lam_mean = piv + M1 / I
+ *   V        = ( sum t[k] (wl[k] - lam_mean)^2 ) / I,   lam_rms = sqrt(V)       centred on the finished mean, a second pass
+ *   e[0]     = wl[0] - dlam[0] / 2,  e[k] = (wl[k-1] + wl[k]) / 2,  e[npix] = wl[npix-1] + dlam[npix-1] / 2        cell edges
+ *   lam_q    : target = q I; k the first pixel for which S[k] < target is false (none: npix - 1); frac = (S[k] - target) / t[k]
+ *              clamped to [0, 1], 0 where t[k] > 0 does not hold; lam_q = e[k+1] - (e[k+1] - e[k]) frac -- continuous across
+ *              pixels, unbiased on a uniform grid
+ *   mom[i, l, :]  = I, lam_mean, lam_rms        batch x nlines x 3
+ *   lamq[i, l, j] = lam_q[j]                    batch x nlines x nq
+ * I not finite or 0: lam_mean, lam_rms and every lam_q are NaN, I stays as computed; nc = 0 gives I = 0 exactly.  A NaN in an
+ * active slot makes that row's outputs NaN and touches no other row; the parameters of the other slots are never read.  Nothing
+ * is convolved, the continuum does not enter, fillers take no part.  A spectrum of several fit ranges has ONE wide dlam at each
+ * gap, as als_fitter.calc_w has: the pixel after a gap weighs its tau with the gap's width.
+ * Either output may be NULL, not both; lamq == NULL exactly when nq == 0; nq <= 16; every q[j] finite and in [0, 1].  No
+ * floating-point atomics, every sum in ONE order (inside a wave of 64 consecutive pixels a fixed scan, the waves in pixel
+ * order), I is the last value of the device's own S: a row's bits do not depend on its batch, its position, the pass it
+ * falls in, nq, the values of q, the outputs requested or the device count.  Row passes hold at most 65535 rows and 384 MiB of
+ * per-row workspace.  MCALF_ERR_INVALID before any device work for: a NULL context, batch < 0, a NULL P with batch > 0, nq
+ * outside [0, 16], nq > 0 with a NULL q or lamq, lamq with nq == 0, a q[j] not finite or outside [0, 1], mom and lamq both
+ * NULL, a spectrum of fewer than 2 pixels.  batch == 0 does nothing.  Host pointers, synchronous; a multi-device context cuts
+ * the rows as mcalf_eqw_batch does. */
+int mcalf_kinematics_batch(mcalf_ctx* ctx, const double* P, int64_t batch, const double* q, int32_t nq, double* mom, double* lamq);
+/* Same, device pointers, on the caller's stream (single-device contexts).  q is a HOST array, read during the call (its values
+ * travel in the kernels' argument block).  After one call of the same or a larger batch and nq it allocates and synchronises
+ * nothing. */
+int mcalf_kinematics_batch_device(mcalf_ctx* ctx, const double* dP, int64_t batch, const double* q, int32_t nq, double* dmom,
+                                  double* dlamq, void* stream);
+
 /* Per-pixel posterior bands of the model over the rows of a chain, on the device, without a spectrum reaching the host (the
  * reference's plot pass overplots 100 sampled spectra instead, mcalf/cli.py:398-418).  With M[i, :] = mcalf_model_batch(P[i],
  * targonly) under the context's conv_mode -- the same kernels, the same bits, wide LSFs and tiled spectra included -- and,

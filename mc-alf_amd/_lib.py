@@ -248,6 +248,8 @@ SYMBOLS = {
     "mcalf_loglike_hvp_batch_device": (C.c_int, [_CTX, _P, _P, C.c_int64, _P, _P]),
     "mcalf_eqw_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, _P]),
     "mcalf_eqw_batch_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    "mcalf_kinematics_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, C.c_int32, _P, _P]),
+    "mcalf_kinematics_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, C.c_int32, _P, _P, _P]),
     "mcalf_model_band_batch": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "mcalf_model_band_batch_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mcalf_fisher_matvec_batch": (C.c_int, [_CTX, _P, _P, C.c_int64, _P]),

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "eqw_args.h"
+#include "tau_fold.h"
 #include "voigt_device.h"
 #include "wave_row.h"
 
@@ -28,42 +29,8 @@ using namespace mcalf;
 
 namespace {
 
-static_assert(kFastMaxA == kYFastMax, "record_kind's fast path is the folded tables' range of a");
-constexpr int kEqwTab = (VT_NTOT + 7) & ~7;       // doubles per folded table in LDS
-static_assert(2 * kEqwBlock >= VT_NTOT, "two coefficients per thread cover the table");
-
 __device__ __forceinline__ int eqw_nrec(const EqwArgs& a) { return a.lay.ncompmax * a.lay.nlines; }
 __device__ __forceinline__ int eqw_ncells(const EqwArgs& a) { return (a.lay.ncompmax + 1) * a.lay.nlines; }
-
-// K H(u, y) of a fast-path line from its folded table: what a directly evaluated pixel of the fused kernel gets
-// (kernels.hip: eval_line) -- the core table for every |u| < 8, the two wing zones in 1/u^2 beyond.
-__device__ __forceinline__ double tau_fast(const double* __restrict__ tab, double u) {
-    const double x2 = u * u;
-    double t, P;
-    if (x2 >= kX2Far) {
-        t = fast_rcp(x2);
-        const double* c = tab + VT_ZF_OFF;
-        P = c[VT_FDEG];
-#pragma unroll
-        for (int k = VT_FDEG - 1; k >= 0; --k) P = fma(P, t, c[k]);
-    } else if (x2 >= kX2Wing) {
-        t = fast_rcp(x2);
-        const double* c = tab + VT_Z0_OFF;
-        P = c[VT_WDEG];
-#pragma unroll
-        for (int k = VT_WDEG - 1; k >= 0; --k) P = fma(P, t, c[k]);
-    } else {                                                  // |u| < 8, or NaN (interval 0, the result is NaN)
-        const double x4 = fabs(u) * 4.0;
-        const int jx = min(max((int)x4, 0), VT_NINT - 1);
-        const double s = fma(x4, 2.0, -(double)(2 * jx + 1));
-        const double* c = tab + jx * VT_CSTRIDE;
-        P = c[VT_CDEG];
-#pragma unroll
-        for (int k = VT_CDEG - 1; k >= 0; --k) P = fma(P, s, c[k]);
-        t = 1.0;
-    }
-    return t * P;
-}
 
 // sum_j (1 - exp(-tau_j)) dlam_j over the thread's valid pixels, in pixel order.
 __device__ __forceinline__ double width_terms(const double (&tau)[kEqwPpt], const double (&dl)[kEqwPpt], unsigned valid) {
@@ -105,18 +72,11 @@ __global__ __launch_bounds__(64) void mcalf_eqw_setup_kernel(const EqwArgs a) {
 }
 
 __global__ __launch_bounds__(kEqwBlock) void mcalf_eqw_pixel_kernel(const EqwArgs a) {
-    __shared__ double sTab[2][kEqwTab];
+    __shared__ double sTab[2][kFoldTab];
     const int r = blockIdx.y, t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
-    // the thread's two coefficients of every fold: table entries t and t + kEqwBlock
-    const int i0 = t, i1 = t + kEqwBlock;
-    const bool has1 = i1 < VT_NTOT;
-    double T0[VT_NY], T1[VT_NY];
-#pragma unroll
-    for (int n = 0; n < VT_NY; ++n) {
-        T0[n] = a.tabs[n * VT_NTOT + i0];
-        T1[n] = has1 ? a.tabs[n * VT_NTOT + i1] : 0.0;
-    }
+    double T0[VT_NY], T1[VT_NY];                                                   // the thread's two coefficients of every fold: table entries t and t + kEqwBlock
+    fold_load<kEqwBlock>(a.tabs, t, T0, T1);
     double nu[kEqwPpt], dl[kEqwPpt];
     unsigned valid = 0;
 #pragma unroll
@@ -146,8 +106,7 @@ __global__ __launch_bounds__(kEqwBlock) void mcalf_eqw_pixel_kernel(const EqwArg
             if (kind == (int)kEqwFast) {
                 const double Kyt = rec[4];
                 double* tab = sTab[buf];
-                tab[i0] = fold_coef(T0, y, K);                                     // (t < kEqwBlock <= VT_NCORE: a core coefficient)
-                if (has1) tab[i1] = fold_coef(T1, y, i1 < VT_NCORE ? K : Kyt);
+                fold_store<kEqwBlock>(tab, T0, T1, t, y, K, Kyt);
                 __syncthreads();                                                   // (the other table is still being read by slower waves)
                 buf ^= 1;
 #pragma unroll

@@ -121,6 +121,7 @@ static int create_impl(const mcalf_spec* sp, mcalf_ctx* ctx) {
     HIP_TRY(ctx, hipMemcpy(ctx->d_lines, tab.lines.data(), tab.lines.size() * sizeof(LineDev), hipMemcpyHostToDevice));
     if ((rc = upload_tables(ctx, &ctx->d_tabs.p))) return rc;
     if ((rc = eqw_prepare(ctx, sp->wl))) return rc;
+    if ((rc = kin_prepare(ctx, sp->wl))) return rc;
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_segok.p, tab.segok.size() * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMemcpy(ctx->d_segok, tab.segok.data(), tab.segok.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMalloc((void**)&ctx->d_wtab.p, sizeof(VT_INTERP_W_HOST)));

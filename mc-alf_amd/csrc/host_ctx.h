@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_nsrun.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_nsrun.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_kin.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.  What a context
 // decides from its spec alone -- the checks, the launch geometry, the host tables -- is ctx_plan.h (no HIP there: the CPU tests
@@ -317,6 +317,11 @@ struct mcalf_ctx : CtxShape {               // (the problem and geometry fields:
     DevBuf<double> d_dlam;
     enum { kEbRecs, kEbPart, kEbCount };
     DevBuf<double> eb[kEbCount];
+    // The optical-depth kinematics entries (host_kin.cpp): the wavelengths [npix] and the cell edges [npix + 1] (none for a
+    // one-pixel spectrum) and the four per-row workspaces of one pass, grown on demand.
+    DevBuf<double> d_wl, d_edge;
+    enum { kKbRecs, kKbPart, kKbHead, kKbCand, kKbCount };
+    DevBuf<double> kb[kKbCount];
     // The posterior-band entries (host_band.cpp), grown on demand: the per-block partials and counts, the per-pixel mean / count
     // a call keeps for itself when the caller wants neither, and the selected order statistics.  The [batch][npix] model matrix
     // is NOT among them: the host entry releases it before it returns, the device entry is handed the caller's.
@@ -588,6 +593,9 @@ inline RowLayout row_layout(const mcalf_ctx* ctx) {
 
 // ---- host_eqw.cpp: the equivalent-width entries -------------------------------------------------------------------------
 int eqw_prepare(mcalf_ctx* ctx, const double* wl);     // mcalf_create: dlam on the device
+
+// ---- host_kin.cpp: the optical-depth kinematics entries -----------------------------------------------------------------
+int kin_prepare(mcalf_ctx* ctx, const double* wl);     // mcalf_create: wl and the cell edges on the device
 
 // ---- comm.cpp -----------------------------------------------------------------------------------------------------------
 void comm_release(mcalf_ctx* ctx);
