@@ -94,7 +94,9 @@ extern "C" {
                                     mcalf_tempered_batch[_device], parallel tempering of that sampler: a ladder of temperatures
                                     moved in the same launches, swaps between neighbours;
                                     mcalf_nested_open / _advance / _finish / _read / _last_round / _close / _footprint /
-                                    _set_timing / _last_times, a nested-sampling run whose live and dead points stay on the device) */
+                                    _set_timing / _last_times, a nested-sampling run whose live and dead points stay on the device;
+                                    mcalf_hmc_batch[_device], Hamiltonian Monte Carlo of independent walkers in the unit cube,
+                                    driven by the analytic gradient) */
 
 enum {
     MCALF_OK = 0,
@@ -717,6 +719,76 @@ int mcalf_tempered_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, con
 int mcalf_tempered_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const double* beta, const mcalf_pt_opts* opts,
                                 double* dU, double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept, int32_t* dnswap,
                                 double* dCU, double* dCL, void* stream);
+
+/* Hamiltonian Monte Carlo: n = nwalkers INDEPENDENT walkers in the unit cube of mcalf_set_prior's box (MCALF_ERR_INVALID if none
+ * is set), each making nsteps iterations of one trajectory of nleap leapfrog steps, in lock step, with a diagonal mass.  The
+ * target is the other samplers': logL, plus lnprior under mcalf_set_gauss_prior; logL is exactly mcalf_loglike_cube_batch's value
+ * and its gradient is mcalf_loglike_grad_batch_device's row.  `scale` [ndim] and `wid` [n] are HOST arrays in both entries, read
+ * during the call as opts is: scale[k] >= 0 is the length of coordinate k in cube units (its inverse square is the mass),
+ * wid[w] the id that keys walker w's random words (NULL: 0 .. n - 1; the ids must be distinct, as the slice step's sid).
+ *   frozen   coordinate k is frozen if it is the ncomp slot (startind of mcalf_info, whatever the int_ncomp flavour), if
+ *            hi_k == lo_k or if scale[k] == 0.  Its momentum is exactly 0, it never moves and does not enter the kinetic
+ *            energy.  So a walker keeps its component count -- different walkers may hold different counts -- and moves that
+ *            change the count belong to the ensemble and the nested samplers.
+ *   gradient with s_k = hi_k - lo_k and theta = u s + lo (the two operations of the cube transform; the ncomp slot truncated as
+ *            there), G the gradient launch's row at theta:  g_k = s_k G_k;  under a Gaussian prior, for every k with
+ *            sigma_k > 0:  d = (theta_k - mu_k) / sigma_k;  t = d / sigma_k;  g_k <- g_k - t s_k  (a product, then a
+ *            difference).  pr = lnprior of the row as mcalf_lnprior_batch gives it, or an exact 0 without a Gaussian.
+ *   start    one gradient launch over all n rows of theta(U0).  A walker whose start has an entry outside [0, 1] or a NaN,
+ *            whose logL is not finite or whose g has a non-finite unfrozen entry has status -1: it never moves and comes back
+ *            as given.  Every other walker has status 0.
+ *   words    g = first_iter + i is the global iteration, w the walker's id, the key (seed, 4); a block is the Philox4x64-10
+ *            function with the constants of the slice step above.  The decision block is the one at counter (g + 1, 2^63, w, 0):
+ *            xi = (w1 >> 11) 2^-53;  zeta = ((w2 >> 11) + 1) 2^-53.  The momentum of unfrozen coordinate k is a standard normal
+ *            by Marsaglia's polar method from the blocks at (g + 1, (a << 32) | k, w, 0), attempts a = 0, 1, ..., 15: with
+ *            x(word) = (word >> 11) 2^-53 the candidate pairs of a block are (v1, v2) = (2 x(w0) - 1, 2 x(w1) - 1), then
+ *            (2 x(w2) - 1, 2 x(w3) - 1);  q = v1 v1 + v2 v2;  the first candidate with 0 < q < 1 gives
+ *            r_k = v1 sqrt((-2 ln q) / q), ln the ensemble sampler's above.  If all 32 candidates fail (probability 4e-22)
+ *            r_k = 0.
+ *   trajectory  eps' = eps (1 + jitter (2 xi - 1));  a_k = eps' scale[k];  h_k = 0.5 a_k;  K0 = 0.5 sum r_k r_k;  y = x,
+ *            gy = g(x).  Each of the nleap steps:  r_k <- r_k + h_k gy_k;  y_k <- y_k + a_k r_k;  ONE reflection -- if
+ *            y_k < 0: y_k <- -y_k, r_k <- -r_k; else if y_k > 1: y_k <- 2 - y_k, r_k <- -r_k;  the gradient launch at
+ *            theta(y);  r_k <- r_k + h_k gy_k with the new gy.  (Two neighbouring half kicks are two additions.)
+ *   dead     a trajectory is dead from the step where a reflected y_k is still outside [0, 1] or is a NaN, where the launch's
+ *            logL is not finite, or where an unfrozen gy_k is not finite.  A dead trajectory puts the walker's own x into its
+ *            row for every later launch, is rejected, and adds one to ndead[w].
+ *   decide   K1 = 0.5 sum r_k r_k;  q = ((L(y) + pr(y)) - (L(x) + pr(x))) + (K0 - K1).  Accepted iff the trajectory is not
+ *            dead and ln zeta < q (any NaN: false):  x <- y, logL <- L(y), g <- gy, naccept + 1.  g is kept across iterations:
+ *            an iteration costs exactly nleap gradient launches.
+ *   chain    the ensemble sampler's: after every iteration i with (i + 1) mod thin == 0 the state goes into slot
+ *            (i + 1) / thin - 1 of CU [nkeep][n][ndim] and CL [nkeep][n], nkeep = nsteps / thin.
+ * Every product, quotient, sum, difference and square root above is ONE correctly rounded IEEE operation (nothing is contracted
+ * to an FMA) and there are no floating-point atomics.  A sum over coordinates is taken as the prior's: a lane adds its
+ * coordinates k, k + 64, ... in index order onto +0.0, then the xor-butterfly 32 .. 1 folds the 64 lanes.  So a run is restated
+ * exactly on the host, given the device's own gradient.  A walker's results depend on its start row, its id, opts and scale
+ * alone -- not on the batch, its position in it or the stream -- and taking the last U as U0 with first_iter advanced by nsteps
+ * is, bit for bit, the longer call.  A leapfrog step is one kernel of the sampler's and one gradient launch over the n rows;
+ * nothing is read back during a call.  theta (optional) holds the transformed rows of U as the cube launch forms them. */
+typedef struct {
+    int32_t nsteps;          /* iterations, >= 0 (0: the checked start, its logL and status) */
+    int32_t thin;            /* every thin-th iteration goes into the chain, >= 1 */
+    int32_t nleap;           /* leapfrog steps of a trajectory, >= 1 */
+    int32_t reserved;
+    double eps;              /* the step size, finite and > 0 */
+    double jitter;           /* its relative jitter per walker and iteration, in [0, 1) */
+    uint64_t seed;           /* the Philox key word 0 */
+    uint64_t first_iter;     /* the iteration number of the call's first iteration (continuation) */
+} mcalf_hmc_opts;            /* 48 bytes */
+/* Host pointers, synchronous: U, theta (n x ndim; theta NULL: not wanted), logL, status, naccept, ndead (n each) and the chain CU,
+ * CL (each NULL: not wanted) are outputs; U0 and U must not overlap.  A multi-device context runs the whole call on its first
+ * device entry, bit for bit a single-device context's result: cutting independent walkers over devices needs a strided copy of
+ * the chain and is left out -- a caller can split the walkers over contexts by wid and gets the same bits.  All argument checks
+ * (ctx, opts or a required array NULL; nwalkers < 0; nsteps < 0; thin < 1; nleap < 1; eps not finite or <= 0; jitter outside
+ * [0, 1); a scale entry negative or not finite; no prior set) come before any device work and name the argument.  A chain above
+ * 4 GiB on the device is MCALF_ERR_RANGE (the ensemble sampler's message).  nwalkers == 0 does nothing. */
+int mcalf_hmc_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, const double* scale, const uint64_t* wid, const mcalf_hmc_opts* opts,
+                    double* U, double* theta, double* logL, int32_t* status, int32_t* naccept, int32_t* ndead, double* CU, double* CL);
+/* Same, device pointers (scale, wid and opts stay host arrays: they travel in kernel argument blocks), on the caller's stream
+ * (single-device contexts).  It never synchronises; the bits are the host entry's.  After one call of the same or a larger size
+ * it allocates nothing. */
+int mcalf_hmc_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const double* scale, const uint64_t* wid,
+                           const mcalf_hmc_opts* opts, double* dU, double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept,
+                           int32_t* dndead, double* dCU, double* dCL, void* stream);
 
 /* A device-resident nested-sampling run: the live set UL [nlive][ndim] / LL [nlive] and the dead rows UD [max_dead][ndim] /
  * LD [max_dead] stay on the device from mcalf_nested_open to mcalf_nested_close; a round transfers no rows, only one record of

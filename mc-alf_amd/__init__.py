@@ -10,6 +10,7 @@ from . import adapters  # noqa: F401
 from . import broker  # noqa: F401
 from . import dist  # noqa: F401
 from . import ensemble  # noqa: F401
+from . import hmc  # noqa: F401
 from . import kinematics  # noqa: F401
 from . import nested  # noqa: F401
 from . import nested_device  # noqa: F401

@@ -174,6 +174,19 @@ class mcalf_pt_opts(C.Structure):
     ]
 
 
+class mcalf_hmc_opts(C.Structure):
+    _fields_ = [
+        ("nsteps", C.c_int32),
+        ("thin", C.c_int32),
+        ("nleap", C.c_int32),
+        ("reserved", C.c_int32),
+        ("eps", C.c_double),
+        ("jitter", C.c_double),
+        ("seed", C.c_uint64),
+        ("first_iter", C.c_uint64),
+    ]
+
+
 class mcalf_nested_opts(C.Structure):
     _fields_ = [
         ("batch", C.c_int32),
@@ -264,6 +277,8 @@ SYMBOLS = {
     "mcalf_ensemble_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_tempered_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_tempered_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_hmc_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_hmc_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_nested_open": (C.c_int, [_CTX, _P, C.c_int64, _P]),
     "mcalf_nested_advance": (C.c_int, [_CTX, C.c_int32, _P]),
     "mcalf_nested_finish": (C.c_int, [_CTX, _P, _P, _P]),

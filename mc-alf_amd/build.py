@@ -1,10 +1,11 @@
 """Build libmcalf_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The library is twenty-nine translation units: the ten device files of DEVICE_OBJECTS -- kernels.hip (the likelihood's
+The library is thirty-one translation units: the eleven device files of DEVICE_OBJECTS -- kernels.hip (the likelihood's
 kernels), grad_kernels.hip (the analytic gradient's and the Jacobian products'), eqw_kernels.hip (the equivalent widths'), kin_kernels.hip (the optical-depth
 kinematics'), band_kernels.hip (the posterior bands'), fit_kernels.hip (the fit's and the Fisher product's), ns_kernels.hip (nested sampling's
 replacement step), ns_round_kernels.hip (the book-keeping of a device-resident nested-sampling run), ens_kernels.hip (the
-ensemble sampler's moves and its temperature swaps) and prior_kernels.hip (the batched lnprior) -- and the host side of the C
+ensemble sampler's moves and its temperature swaps), hmc_kernels.hip (Hamiltonian Monte Carlo's integrator and accept rule)
+and prior_kernels.hip (the batched lnprior) -- and the host side of the C
 ABI, HOST_SOURCES, compiled as plain C++ against the HIP runtime API.  Objects are kept under csrc/obj/ so that an edit of a host file does not recompile
 the kernels (22 s), and an edit of one device file does not recompile the others."""
 from __future__ import annotations
@@ -31,16 +32,17 @@ DEVICE_OBJECTS = {
     "fit_kernels.hip": ["fit_args.h", "theta_row.h", "wave_row.h", "kernel_args.h"],
     "ns_kernels.hip": ["ns_args.h", "wave_row.h", "prior_device.h", "prior_args.h", "kernel_args.h"],
     "ns_round_kernels.hip": ["ns_round_args.h", "wave_row.h", "kernel_args.h"],
-    "ens_kernels.hip": ["ens_args.h", "wave_row.h", "prior_device.h", "prior_args.h", "kernel_args.h"],
+    "ens_kernels.hip": ["ens_args.h", "ens_ln.h", "wave_row.h", "prior_device.h", "prior_args.h", "kernel_args.h"],
+    "hmc_kernels.hip": ["hmc_args.h", "ens_ln.h", "wave_row.h", "prior_device.h", "prior_args.h", "kernel_args.h"],
     "prior_kernels.hip": ["prior_args.h", "prior_device.h", "wave_row.h", "kernel_args.h"],
 }
 DEVICE_SOURCES = list(DEVICE_OBJECTS)
 # the device files whose kernels' resource usage a verbose build prints (all but the gradient's)
 REPORTED = [s for s in DEVICE_SOURCES if s != "grad_kernels.hip"]
 HOST_SOURCES = ["host_abi.cpp", "host_launch.cpp", "host_wide.cpp", "host_pipeline.cpp", "host_stream.cpp", "host_config.cpp", "host_multi.cpp",
-                "host_staged.cpp", "host_grad.cpp", "host_fit.cpp", "host_ns.cpp", "host_nsrun.cpp", "host_ens.cpp", "host_prior.cpp", "host_eqw.cpp", "host_kin.cpp", "host_band.cpp", "broker.cpp", "comm.cpp"]
+                "host_staged.cpp", "host_grad.cpp", "host_fit.cpp", "host_ns.cpp", "host_nsrun.cpp", "host_ens.cpp", "host_hmc.cpp", "host_prior.cpp", "host_eqw.cpp", "host_kin.cpp", "host_band.cpp", "broker.cpp", "comm.cpp"]
 SOURCES = DEVICE_SOURCES + HOST_SOURCES
-HOST_HEADERS = ["host_ctx.h", "ctx_plan.h", "kernel_args.h", "theta_row.h", "grad_args.h", "eqw_args.h", "kin_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ns_round_args.h", "ns_evidence.h", "ens_args.h", "prior_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
+HOST_HEADERS = ["host_ctx.h", "ctx_plan.h", "kernel_args.h", "theta_row.h", "grad_args.h", "eqw_args.h", "kin_args.h", "band_args.h", "fit_args.h", "ns_args.h", "ns_round_args.h", "ns_evidence.h", "ens_args.h", "hmc_args.h", "prior_args.h", "voigt_tables.h", os.path.join("..", "..", "include", "mcalf_hip.h")]
 TARGET = os.path.join(CSRC, "libmcalf_hip.so")
 OBJDIR = os.path.join(CSRC, "obj")
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")

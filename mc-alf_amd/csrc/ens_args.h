@@ -1,5 +1,5 @@
 // What the ensemble-sampler kernels (ens_kernels.hip) and their host side (host_ens.cpp) share: the argument block, the
-// workspace layout, the constants of the fixed-sequence logarithm and the kernel handles.  Plain C++ -- host_ens.cpp is compiled
+// workspace layout and the kernel handles.  Plain C++ -- host_ens.cpp is compiled
 // without the HIP language mode.
 // Not part of the kernel-source hash (mc-alf_amd/build.py): the fused kernel does not include it.
 #pragma once
@@ -22,17 +22,7 @@ constexpr int kEnsMaxTemps = 64;         // temperatures of one call at most: th
 enum { kEnsOk = 0, kEnsBadStart = -1 };
 enum { kEnsStretch = 0, kEnsDE = 1 };
 
-// ens_ln(x), x normal and positive: a fixed sequence of IEEE operations (tests/ens_reference.py restates it in numpy).
-//   e, f   x = f 2^e with f in [1, 2), from the bits;  if f > kEnsSqrt2: f <- 0.5 f (exact), e <- e + 1
-//   r      = (f - 1) / (f + 1)             (f - 1 is exact; |r| <= 0.1716)
-//   s      = r r
-//   p      = c9;  p <- p s + c_i for i = 8 .. 1, with c_i = 1 / (2 i + 1)  (each step a product and a sum)
-//   t      = r + r;  lnf = t + (t s) p     (the odd series 2 r (1 + s / 3 + s^2 / 5 + ...), cut after s^9 / 19: the next
-//                                           term is below 2.3e-17 of the sum)
-//   ln x   = e kEnsLn2Hi + (lnf + e kEnsLn2Lo)    (kEnsLn2Hi has 21 trailing zero bits: e kEnsLn2Hi is exact)
-constexpr double kEnsSqrt2 = 0x1.6a09e667f3bcdp+0;
-constexpr double kEnsLn2Hi = 0x1.62e42feep-1, kEnsLn2Lo = 0x1.a39ef35793c76p-33;
-constexpr int kEnsLnTerms = 9;
+// (ens_ln(x), the fixed-sequence logarithm, and its constants: ens_ln.h, which hmc_kernels.hip includes as well)
 
 // One half-step, or one swap round, of one call: T = ntemps temperatures of n walkers each (mcalf_ensemble_batch: T = 1 with
 // beta[0] = 1).  Row t n + w is walker w of temperature t; a half-step moves the T m rows t n + half m + b, trial row t m + b

@@ -27,31 +27,11 @@
 
 #pragma clang fp contract(off)
 
+#include "ens_ln.h"
 #include "prior_device.h"
 #include "wave_row.h"
 
 using namespace mcalf;
-
-namespace {
-
-// ln x for normal positive x: the sequence of ens_args.h, operation for operation.
-__device__ __forceinline__ double ens_ln(double x) {
-    const long long b = __double_as_longlong(x);
-    int e = (int)((b >> 52) & 0x7ff) - 1023;
-    double f = __longlong_as_double((b & 0x000fffffffffffffLL) | 0x3ff0000000000000LL);
-    if (f > kEnsSqrt2) { f = f * 0.5; e += 1; }
-    const double r = (f - 1.0) / (f + 1.0);
-    const double s = r * r;
-    double p = 1.0 / (2 * kEnsLnTerms + 1);
-#pragma unroll
-    for (int i = kEnsLnTerms - 1; i >= 1; --i) p = p * s + 1.0 / (2 * i + 1);
-    const double t = r + r;
-    const double lnf = t + (t * s) * p;
-    const double ed = (double)e;
-    return ed * kEnsLn2Hi + (lnf + ed * kEnsLn2Lo);
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(kEnsWave) void mcalf_ens_start_kernel(const EnsArgs a) {
     const int w = blockIdx.x, lane = threadIdx.x;              // (a row of the T n)

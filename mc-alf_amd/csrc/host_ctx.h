@@ -1,4 +1,4 @@
-// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_nsrun.cpp, host_ens.cpp, host_prior.cpp, host_eqw.cpp, host_kin.cpp, host_band.cpp, broker.cpp, comm.cpp):
+// Host side of libmcalf_hip.so, shared by its translation units (host_abi.cpp, host_launch.cpp, host_wide.cpp, host_pipeline.cpp, host_stream.cpp, host_staged.cpp, host_grad.cpp, host_fit.cpp, host_ns.cpp, host_nsrun.cpp, host_ens.cpp, host_hmc.cpp, host_prior.cpp, host_eqw.cpp, host_kin.cpp, host_band.cpp, broker.cpp, comm.cpp):
 // the context behind the opaque mcalf_ctx of include/mcalf_hip.h and the internal functions one file offers the others.
 // Plain C++ against the HIP runtime API; kernels are launched through the entry-point table of kernel_args.h.  What a context
 // decides from its spec alone -- the checks, the launch geometry, the host tables -- is ctx_plan.h (no HIP there: the CPU tests
@@ -359,6 +359,13 @@ struct mcalf_ctx : CtxShape {               // (the problem and geometry fields:
     DevBuf<double> enb[kEnCount];
     DevBuf<int32_t> ens_inside;
     DevBuf<double> ens_pr;                  // lnprior of the walkers [T n], grown by a call under a Gaussian prior only
+    // Hamiltonian Monte Carlo (host_hmc.cpp), grown on demand.  The walkers' cube gradient, the momenta, the trajectories'
+    // positions, their theta rows and the gradient rows the launch leaves [n][ndim] each; its logL [n]; K0 and lnprior [2][n];
+    // the call's scale [ndim]; the dead flags [n] and the walker ids [n].  The chain is NOT among them, as the ensemble's.
+    enum { kHmG, kHmR, kHmY, kHmTheta, kHmGY, kHmLY, kHmAux, kHmScale, kHmCount };
+    DevBuf<double> hmb[kHmCount];
+    DevBuf<int32_t> hmc_dead;
+    DevBuf<uint64_t> hmc_wid;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields, its CtxShape, are a copy of sub-context 0's, for mcalf_info).
@@ -567,6 +574,9 @@ struct Product {
 };
 extern const Product kProdGrad, kProdJvp, kProdVjp, kProdHvp;
 int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStream_t stream);   // product `p` over device rows, on `stream`
+// What host_hmc.cpp puts between its own kernels, next to cube_logl / cube_to_theta: logL into L and the gradient rows into G
+// for the `n` device theta rows at P, exactly what mcalf_loglike_grad_batch_device(P) issues and writes.
+int theta_logl_grad(mcalf_ctx* ctx, const double* P, double* L, double* G, int64_t n, hipStream_t stream);
 
 // ---- host_ns.cpp: the replacement step, for host_nsrun.cpp ---------------------------------------------------------------
 // The device rows of one call of the replacement primitive.

@@ -115,6 +115,10 @@ int run_product(mcalf_ctx* ctx, const Product& p, Call c, int64_t batch, hipStre
     return MCALF_OK;
 }
 
+int theta_logl_grad(mcalf_ctx* ctx, const double* P, double* L, double* G, int64_t n, hipStream_t stream) {
+    return run_product(ctx, kProdGrad, {P, nullptr, G, L}, n, stream);
+}
+
 namespace {
 
 int run_device(mcalf_ctx* ctx, const Product& p, const Call& c, int64_t batch, void* stream) {
