@@ -1,9 +1,9 @@
-// Device helpers of the kernels that give ONE wave64 to a row (fit_kernels.hip, ns_kernels.hip, ens_kernels.hip): lane k owns
-// coordinates k, k + 64, ...; a row's scalars are folded over the lanes by one fixed xor-butterfly and made wave-uniform with
-// readfirstlane; the random words of a row are Philox4x64-10 blocks.  (eqw_kernels.hip takes wave_sum alone, for its waves' partials.)
+// Device helpers of the kernels that give ONE wave64 to a row: lane k owns coordinates k, k + 64, ...; a row's scalars are
+// folded over the lanes by one fixed xor-butterfly and made wave-uniform with readfirstlane; the random words of a row are
+// Philox4x64-10 blocks.  (A kernel that gives a row several waves may take wave_sum alone, for its waves' partials.)
 // The only floating-point arithmetic in here is wave_sum's add, which has no product to contract with: it does not matter
-// whether the including file has switched contraction to FMA off (ns_kernels.hip and ens_kernels.hip do, before they include
-// this; fit_kernels.hip does not).
+// whether the including file has switched contraction to FMA off before it includes this (the samplers' files do) or has
+// left it on.
 // Not part of the kernel-source hash (mc-alf_amd/build.py): the fused kernel does not include it.
 #pragma once
 #include <hip/hip_runtime.h>

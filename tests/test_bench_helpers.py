@@ -71,7 +71,7 @@ def test_library_carries_the_hash_of_the_device_sources():
     assert bld.HASHED[0] == "kernels.hip" and len(set(bld.HASHED)) == len(bld.HASHED)
     assert sorted(bld.HASHED) == sorted(reached)
     assert {"kernel_args.h", "voigt_device.h", "voigt_tables.h"} < set(bld.HASHED)
-    assert bld.DEVICE_OBJECTS["kernels.hip"] == bld.HASHED[1:]
+    assert set(bld.closure("kernels.hip")) == set(reached) - {"kernels.hip"}   # (what build.py rebuilds kernels.o for)
     assert not set(bld.HASHED) & set(bld.HOST_SOURCES)
     kernels = open(os.path.join(bld.CSRC, "kernels.hip")).read()
     assert 'extern "C"' not in kernels and "__global__" in kernels
