@@ -96,7 +96,10 @@ extern "C" {
                                     mcalf_nested_open / _advance / _finish / _read / _last_round / _close / _footprint /
                                     _set_timing / _last_times, a nested-sampling run whose live and dead points stay on the device;
                                     mcalf_hmc_batch[_device], Hamiltonian Monte Carlo of independent walkers in the unit cube,
-                                    driven by the analytic gradient) */
+                                    driven by the analytic gradient;
+                                    mcalf_chain_stats[_device], chain diagnostics on the device: autocorrelation time, split
+                                    R-hat and effective sample size, and mcalf_ensemble_converge[_device], the ensemble sampler
+                                    run until they say it has converged) */
 
 enum {
     MCALF_OK = 0,
@@ -789,6 +792,96 @@ int mcalf_hmc_batch(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, const do
 int mcalf_hmc_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const double* scale, const uint64_t* wid,
                            const mcalf_hmc_opts* opts, double* dU, double* dtheta, double* dlogL, int32_t* dstatus, int32_t* dnaccept,
                            int32_t* dndead, double* dCU, double* dCL, void* stream);
+
+/* Chain diagnostics: per coordinate k of a chain X [T][n][d] (T = nkeep kept steps, n = nwalkers, d = ndim, the chain's OWN width:
+ * any d >= 1, not tied to the context's -- a chain of theta rows or of derived quantities is as good as one of cube rows; row
+ * (t, w, .) is d contiguous doubles, as CU of the samplers) the pooled mean and variance, the walker-averaged integrated
+ * autocorrelation time with Sokal's window, the same of the ensemble-mean series, split R-hat and the effective sample size.
+ * A walker w with status[w] != 0 is left out of everything (status NULL: all are used); nok is the number of walkers used.
+ * With x_t = X[t][w][k], sums over t taken t ascending from +0.0:
+ *   per walker  S_w = sum_t x_t;  mu_w = S_w / T;  h = T / 2 (integer);  m_w1 = (sum_{t < h} x_t) / h,  m_w2 = (sum_{t >= T - h} x_t) / h
+ *            (for odd T the middle state is in neither half).  A series with x_t == x_0 for every t is CONSTANT: its mu_w, m_w1 and
+ *            m_w2 are x_0 by definition, not the rounded sums' (T copies of 0.3 do not add up to 0.3 T), so that its c_w(0) below
+ *            is 0 exactly.  Then, in a second pass,
+ *            c_w(0) = sum_t (x_t - mu_w)^2 by one fma per step;  q_w = sum_t (x_t - mean)^2;
+ *            s2_w1 = (sum_{t < h} (x_t - m_w1)^2) / (h - 1),  s2_w2 likewise over the last h states.
+ *   walker sums  a sum over walkers is taken in ONE fixed order: lane l of 64 adds the used walkers l, l + 64, ... in that order
+ *            from +0.0, then the xor-butterfly 32 .. 1 folds the 64 lanes, as the prior's sums are folded.
+ *   mean, var  mean = (sum_w S_w) / (T nok);  var = (sum_w q_w) / (T nok - 1): pooled over the T nok values, two-pass, ddof 1
+ *            (NaN when nok = 0).  Where every used walker is constant at ONE value v (a frozen coordinate) mean and mbar below are
+ *            v: var is 0 and W is 0, exactly.
+ *   rhat     split R-hat over the 2 nok half chains:  mbar = (sum_w (m_w1 + m_w2)) / (2 nok);  W = (sum_w (s2_w1 + s2_w2)) / (2 nok);
+ *            B = h (sum_w ((m_w1 - mbar)^2 + (m_w2 - mbar)^2)) / (2 nok - 1);  rhat = sqrt(((h - 1) / h W + B / h) / W), NaN where W == 0.
+ *   ACF      L = max_lag, or T - 1 when max_lag == 0.  c_w(tau) = sum_{t = 0}^{T - 1 - tau} (x_t - mu_w) (x_{t + tau} - mu_w) for
+ *            tau = 0 .. L, t ascending, one fma per step (the biased sum the zero-padded FFT route gives; at tau = 0 it is
+ *            c_w(0) above bit for bit).  rho_w(tau) = c_w(tau) / c_w(0).  A walker with c_w(0) == 0 is constant in this
+ *            coordinate (it is stuck, or the coordinate is frozen) and is left out; nused is the number that remain.  The used
+ *            walkers are cut into blocks of 64 consecutive walker indices; a block adds its rho_w(tau) w ascending from +0.0,
+ *            the blocks are added in block order from +0.0, and rho(tau) = that sum / nused.  rho(0) = 1.
+ *   tau, M   tau(m) = 2 (sum_{t <= m} rho(t)) - 1, the sum running from +0.0;  M = the smallest m in [0, L] with m >= c tau(m),
+ *            tau = tau(M), flag bit 0 set ("window reached").  If there is none: M = L, tau = tau(L), bit 0 clear.  nused == 0
+ *            makes rho, and so tau, NaN.  tau is in kept steps.
+ *   tau_mean, M_mean, flag bit 1   the same rule, the same sums, on the ONE series m_t = (sum_w x_t,w) / nok (w ascending over the
+ *            used walkers) as a chain of one walker, constancy decided in the same way: NaN when that series has no variance.
+ *   ess      nok T / tau.
+ * A NaN anywhere in coordinate k of a used walker makes every floating-point output of coordinate k NaN (its M and M_mean are L,
+ * its flags clear; c_w(0) = NaN is not 0, so the walker counts in nused) and touches no other coordinate.
+ * stats [d][6] = mean, var, tau, tau_mean, rhat, ess;  info [d][4] = M, M_mean, nused, flags;  acf [d][L + 1] = rho (NULL: not
+ * wanted).  There are no floating-point atomics and every sum has one order: the bits of every output depend on (X, status,
+ * opts) alone, not on the device's CU count, the stream or the entry.  The walker blocks' partial sums live in a workspace of
+ * the context of ceil(n / 64) d (L + 1) doubles; above 1 GiB the call is refused with MCALF_ERR_RANGE and the message names the
+ * largest max_lag that fits. */
+typedef struct {
+    double c;                /* Sokal's window constant, finite and > 0 */
+    int64_t max_lag;         /* 0: L = nkeep - 1; else L = max_lag in [1, nkeep - 1] */
+} mcalf_chain_opts;          /* 16 bytes */
+/* Host pointers, synchronous.  A multi-device context runs the call on its first device entry.  All argument checks (X, opts,
+ * stats or info NULL; nkeep < 4 -- split R-hat needs halves of at least 2; nwalkers < 1; ndim < 1; c not finite or <= 0; max_lag
+ * outside {0} and [1, nkeep - 1]; sizes that overflow) come before any device work and name the argument, ctx NULL last. */
+int mcalf_chain_stats(mcalf_ctx* ctx, const double* X, int64_t nkeep, int64_t nwalkers, int32_t ndim, const int32_t* status,
+                      const mcalf_chain_opts* opts, double* stats, int32_t* info, double* acf);
+/* Same, device pointers (opts is a host struct), on the caller's stream (single-device contexts).  It never synchronises; the
+ * bits are the host entry's.  After one call of the same or a larger size it allocates nothing. */
+int mcalf_chain_stats_device(mcalf_ctx* ctx, const double* dX, int64_t nkeep, int64_t nwalkers, int32_t ndim, const int32_t* dstatus,
+                             const mcalf_chain_opts* opts, double* dstats, int32_t* dinfo, double* dacf, void* stream);
+
+/* The ensemble sampler run until its chain has converged, or for opts->nsteps iterations at the most.  U0, opts and the outputs
+ * U .. CL are mcalf_ensemble_batch's, CU and CL sized for nkeep = nsteps / thin slots; CU is required here (the statistics are
+ * its), nwalkers >= 4.  The run is a sequence of ensemble calls ("blocks") of check_every thin iterations each (a shorter last
+ * one if nsteps is not a multiple; the nsteps mod thin iterations behind the last kept step are not made), each continuing the one before through first_iter and writing the next slots of the ONE
+ * device chain.  A block starts as every ensemble call does -- the start kernel and one likelihood launch over all nwalkers rows
+ * -- and the walkers it starts from are a device copy of the last block's: one likelihood evaluation per walker and block on top
+ * of the plain run's 2 x check_every x thin half-launches.  After each block, with T kept steps so far and T >= 4, a CHECK takes the statistics above of the chain prefix
+ * CU [0, T) with c = conv->c, status = the walkers' and L = min(T - 1, ceil(c T / factor) + 1) -- no converged verdict can need
+ * a longer lag: M ~ c tau <= c T / factor.  A coordinate is live when its nused > 0 (frozen coordinates are skipped).  The run
+ * stops at the first check j >= 2 (counted from 1) at which every live coordinate has its window reached (flag bit 0),
+ * T >= factor tau and |tau - tau of check j - 1| <= rtol tau; a NaN tau on a live coordinate never converges.
+ *   nkept      T at the stop, or nsteps / thin if the run never stopped; converged 0 or 1; nchecks the checks made
+ *   tau_hist   [nchecks][ndim] the tau of every check (kept steps); capacity ceil((nsteps / thin) / check_every) rows
+ *   stats, info  [ndim][6], [ndim][4]: those of the last check (zero if there was none)
+ * Because a continued ensemble call is the longer call bit for bit and blocks end on kept steps, U, theta, logL, status, naccept
+ * and the first nkept slots of CU and CL are, bit for bit, those of mcalf_ensemble_batch with nsteps = nkept thin (naccept is the
+ * sum of the blocks'); slots past nkept are not written.  Argument checks: conv, nkept, converged, nchecks, tau_hist, stats, info
+ * or CU NULL; check_every < 1; factor, rtol or c not finite, factor or c <= 0, rtol < 0; then mcalf_ensemble_batch's, the 4 GiB
+ * limit on the chain included; all before any device work, ctx NULL among the last. */
+typedef struct {
+    int32_t check_every;     /* kept steps between checks, >= 1 */
+    int32_t reserved;
+    double factor;           /* the run is long enough at T >= factor tau; finite and > 0 */
+    double rtol;             /* tau has settled at |tau - tau_previous| <= rtol tau; finite and >= 0 */
+    double c;                /* Sokal's window constant, finite and > 0 */
+} mcalf_converge_opts;       /* 32 bytes */
+/* Host pointers, synchronous.  A multi-device context runs the whole call on its first device entry. */
+int mcalf_ensemble_converge(mcalf_ctx* ctx, const double* U0, int64_t nwalkers, const mcalf_ens_opts* opts, const mcalf_converge_opts* conv,
+                            double* U, double* theta, double* logL, int32_t* status, int32_t* naccept, double* CU, double* CL,
+                            int64_t* nkept, int32_t* converged, int32_t* nchecks, double* tau_hist, double* stats, int32_t* info);
+/* Same with dU0, dU .. dCL, dstats and dinfo device pointers, on the caller's stream (single-device contexts); nkept, converged,
+ * nchecks and tau_hist stay HOST outputs.  After every check it copies the ndim values of tau and the flags to the host and
+ * waits for the stream: it is the one entry of the sampler family that synchronises.  The bits are the host entry's. */
+int mcalf_ensemble_converge_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, const mcalf_ens_opts* opts,
+                                   const mcalf_converge_opts* conv, double* dU, double* dtheta, double* dlogL, int32_t* dstatus,
+                                   int32_t* dnaccept, double* dCU, double* dCL, int64_t* nkept, int32_t* converged, int32_t* nchecks,
+                                   double* tau_hist, double* dstats, int32_t* dinfo, void* stream);
 
 /* A device-resident nested-sampling run: the live set UL [nlive][ndim] / LL [nlive] and the dead rows UD [max_dead][ndim] /
  * LD [max_dead] stay on the device from mcalf_nested_open to mcalf_nested_close; a round transfers no rows, only one record of

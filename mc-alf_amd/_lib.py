@@ -187,6 +187,23 @@ class mcalf_hmc_opts(C.Structure):
     ]
 
 
+class mcalf_chain_opts(C.Structure):
+    _fields_ = [
+        ("c", C.c_double),
+        ("max_lag", C.c_int64),
+    ]
+
+
+class mcalf_converge_opts(C.Structure):
+    _fields_ = [
+        ("check_every", C.c_int32),
+        ("reserved", C.c_int32),
+        ("factor", C.c_double),
+        ("rtol", C.c_double),
+        ("c", C.c_double),
+    ]
+
+
 class mcalf_nested_opts(C.Structure):
     _fields_ = [
         ("batch", C.c_int32),
@@ -279,6 +296,10 @@ SYMBOLS = {
     "mcalf_tempered_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_hmc_batch": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_hmc_batch_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_chain_stats": (C.c_int, [_CTX, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    "mcalf_chain_stats_device": (C.c_int, [_CTX, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mcalf_ensemble_converge": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcalf_ensemble_converge_device": (C.c_int, [_CTX, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcalf_nested_open": (C.c_int, [_CTX, _P, C.c_int64, _P]),
     "mcalf_nested_advance": (C.c_int, [_CTX, C.c_int32, _P]),
     "mcalf_nested_finish": (C.c_int, [_CTX, _P, _P, _P]),

@@ -181,3 +181,7 @@ const void* ens_kernel_ptr(EnsKernel k) {
     return table[k];
 }
 }  // namespace mcalf
+
+// The chain-diagnostics kernels (mcalf_chain_stats, mcalf_ensemble_converge): one device translation unit with the sampler whose
+// chain they read.  (Not a stand-alone header: it must come last, under this file's `fp contract(off)`.)
+#include "chain_kernels.h"

@@ -366,6 +366,11 @@ struct mcalf_ctx : CtxShape {               // (the problem and geometry fields:
     DevBuf<double> hmb[kHmCount];
     DevBuf<int32_t> hmc_dead;
     DevBuf<uint64_t> hmc_wid;
+    // The chain diagnostics (host_chain.h), grown on demand.  chain_ws: the per-walker sums, the ensemble-mean series, the walker
+    // blocks' partial ACFs and the ACF of one statistics pass, carved per call.  The run to convergence: the walkers a block
+    // starts from [n][ndim] and the block's own accept counts [n].
+    DevBuf<double> chain_ws, chain_u;
+    DevBuf<int32_t> chain_acc;
     // Single-process multi-device context (mcalf_create_multi, host_multi.cpp): the parent holds one complete context per
     // device entry and a worker thread for each but the first; it owns no device memory itself (its problem / geometry
     // fields, its CtxShape, are a copy of sub-context 0's, for mcalf_info).

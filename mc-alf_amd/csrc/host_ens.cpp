@@ -225,3 +225,7 @@ extern "C" int mcalf_tempered_batch_device(mcalf_ctx* ctx, const double* dU0, in
     if (nwalkers == 0) return MCALF_OK;
     return ens_device(ctx, r, nwalkers, *opts, beta, (hipStream_t)stream);
 }
+
+// The chain diagnostics and the run to convergence, which drives run_ens above in blocks: one translation unit with the sampler.
+// (Not a stand-alone header: it defines C entries and must come last, behind run_ens and ens_check.)
+#include "host_chain.h"
