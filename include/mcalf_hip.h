@@ -799,11 +799,14 @@ int mcalf_hmc_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, 
  * autocorrelation time with Sokal's window, the same of the ensemble-mean series, split R-hat and the effective sample size.
  * A walker w with status[w] != 0 is left out of everything (status NULL: all are used); nok is the number of walkers used.
  * With x_t = X[t][w][k], sums over t taken t ascending from +0.0:
- *   per walker  S_w = sum_t x_t;  mu_w = S_w / T;  h = T / 2 (integer);  m_w1 = (sum_{t < h} x_t) / h,  m_w2 = (sum_{t >= T - h} x_t) / h
- *            (for odd T the middle state is in neither half).  A series with x_t == x_0 for every t is CONSTANT: its mu_w, m_w1 and
- *            m_w2 are x_0 by definition, not the rounded sums' (T copies of 0.3 do not add up to 0.3 T), so that its c_w(0) below
- *            is 0 exactly.  Then, in a second pass,
- *            c_w(0) = sum_t (x_t - mu_w)^2 by one fma per step;  q_w = sum_t (x_t - mean)^2;
+ *   per walker  S_w = sum_t x_t;  delta_w = (sum_t (x_t - x_0)) / T;  h = T / 2 (integer);  m_w1 = (sum_{t < h} x_t) / h,  m_w2 = (sum_{t >= T - h} x_t) / h
+ *            (for odd T the middle state is in neither half).  A series with x_t == x_0 for every t is CONSTANT: its m_w1 and
+ *            m_w2 are x_0 by definition, not the rounded sums' (T copies of 0.3 do not add up to 0.3 T), and its centred values
+ *            are 0, so that its c_w(0) below is 0 exactly.  The centred value of any other series is
+ *            xc_t = (x_t - x_0) - delta_w, both differences rounded: x_t - x_0 is exact for values within a factor of two of
+ *            each other, so a walker that has hardly moved keeps its digits (x_t - S_w / T would lose those of x_0 / |xc_t|).
+ *            Then, in a second pass,
+ *            c_w(0) = sum_t xc_t^2 by one fma per step;  q_w = sum_t (x_t - mean)^2;
  *            s2_w1 = (sum_{t < h} (x_t - m_w1)^2) / (h - 1),  s2_w2 likewise over the last h states.
  *   walker sums  a sum over walkers is taken in ONE fixed order: lane l of 64 adds the used walkers l, l + 64, ... in that order
  *            from +0.0, then the xor-butterfly 32 .. 1 folds the 64 lanes, as the prior's sums are folded.
@@ -812,7 +815,7 @@ int mcalf_hmc_batch_device(mcalf_ctx* ctx, const double* dU0, int64_t nwalkers, 
  *            v: var is 0 and W is 0, exactly.
  *   rhat     split R-hat over the 2 nok half chains:  mbar = (sum_w (m_w1 + m_w2)) / (2 nok);  W = (sum_w (s2_w1 + s2_w2)) / (2 nok);
  *            B = h (sum_w ((m_w1 - mbar)^2 + (m_w2 - mbar)^2)) / (2 nok - 1);  rhat = sqrt(((h - 1) / h W + B / h) / W), NaN where W == 0.
- *   ACF      L = max_lag, or T - 1 when max_lag == 0.  c_w(tau) = sum_{t = 0}^{T - 1 - tau} (x_t - mu_w) (x_{t + tau} - mu_w) for
+ *   ACF      L = max_lag, or T - 1 when max_lag == 0.  c_w(tau) = sum_{t = 0}^{T - 1 - tau} xc_t xc_{t + tau} for
  *            tau = 0 .. L, t ascending, one fma per step (the biased sum the zero-padded FFT route gives; at tau = 0 it is
  *            c_w(0) above bit for bit).  rho_w(tau) = c_w(tau) / c_w(0).  A walker with c_w(0) == 0 is constant in this
  *            coordinate (it is stuck, or the coordinate is frozen) and is left out; nused is the number that remain.  The used

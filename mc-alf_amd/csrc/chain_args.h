@@ -37,7 +37,7 @@ struct ChainArgs {
     const int32_t* status;    // [n] or NULL (all walkers used)
     double* sum;              // sum_t x_t
     double* kf;               // 1.0 where x_t == x_0 for every t (a constant series), else 0.0
-    double* mu;               // mu_w = sum / T; x_0 for a constant series (and so the half means)
+    double* mu;               // delta_w = (sum (x_t - x_0)) / T, the centring of the ACF; x_0 for a constant series (and so the half means)
     double* c0;               // c_w(0) = sum_t (x_t - mu_w)^2, t ascending, one fma per step: the lag kernel's tau = 0 sum, bit for bit
     double* sq;               // sum_t (x_t - mean)^2, mean the pooled mean
     double* hm;               // [2][n][d] means of the first and the last h = T / 2 states
@@ -57,7 +57,7 @@ struct ChainArgs {
 
 // The kernels of chain_kernels.h; all take (const ChainArgs a).
 enum ChainKernel {
-    kChainSums,       // grid ceil(n d / 256), 256 threads: per (w, k) sum, mu and the two half means, t ascending
+    kChainSums,       // grid ceil(n d / 256), 256 threads: per (w, k) sum, delta and the two half means, t ascending
     kChainPoolMean,   // grid d, 64 threads: nok, the pooled mean and the mean of the half means over the used walkers
     kChainCentred,    // grid ceil(n d / 256), 256 threads: per (w, k) c0, sq and the two half variances, t ascending
     kChainMeanSeries, // grid T, 64 threads: m_t per coordinate, w ascending

@@ -6,9 +6,11 @@
 // separately rounded but for the explicit fma of the autocovariance sums.  NOT a stand-alone header: it defines kernels and
 // a kernel table, opens namespace mcalf at file scope and relies on the includer's pragma; nothing else may include it.
 //
-//   sums         one thread per (w, k), t ascending: S_w = sum x_t, mu_w = S_w / T, the means of the first and last h = T / 2 states;
-//                a series with x_t == x_0 for every t is CONSTANT and has mu_w and its half means = x_0 (a rounded sum of T
-//                copies of 0.3 over T is not 0.3), so that its c_w(0) is 0 exactly and it is left out.
+//   sums         one thread per (w, k), t ascending: S_w = sum x_t, delta_w = (sum (x_t - x_0)) / T, the means of the first and last
+//                h = T / 2 states; a series with x_t == x_0 for every t is CONSTANT and has its half means = x_0 (a rounded sum of T
+//                copies of 0.3 over T is not 0.3) and c_w(0) = 0 exactly, and it is left out.  The centred value of the ACF is
+//                (x_t - x_0) - delta_w: x_t - x_0 is exact for values within a factor of two of each other, so a walker that has
+//                moved by 1e-5 of its position keeps all its digits, where x_t - S_w / T would keep eleven of sixteen.
 //                Thread w d + k reads X[t n d + w d + k]: a wave reads 512 contiguous bytes per step.
 //   pool mean    one wave per coordinate: nok, mean = (sum_w S_w) / (T nok), the mean of the 2 nok half means (both v where every
 //                used walker is constant at the one value v).  Lane l adds walkers
@@ -48,19 +50,20 @@ __global__ __launch_bounds__(256) void mcalf_chain_sums_kernel(const ChainArgs a
     const int64_t T = a.T, h = T / 2;
     const double* x = a.X + i;
     const double x0 = x[0];
-    double s = 0.0, s1 = 0.0, s2 = 0.0;
+    double s = 0.0, sd = 0.0, s1 = 0.0, s2 = 0.0;
     bool konst = true;                                    // x_t == x_0 for every t (a NaN is equal to nothing: not constant)
     for (int64_t t = 0; t < T; ++t) {
         const double v = x[(size_t)t * nd];
         konst = konst && v == x0;
         s += v;
+        sd += v - x0;
         if (t < h) s1 += v;
         if (t >= T - h) s2 += v;
     }
-    // A constant series has its means by definition, not by a rounded sum: x_t - mu_w is then 0 and c_w(0) == 0 exactly.
+    // A constant series has its means by definition, not by a rounded sum, and its centred values are 0: c_w(0) == 0 exactly.
     a.sum[i] = s;
     a.kf[i] = konst ? 1.0 : 0.0;
-    a.mu[i] = konst ? x0 : s / (double)T;
+    a.mu[i] = konst ? x0 : sd / (double)T;               // (x_0 of a constant series: pool mean compares them)
     a.hm[i] = konst ? x0 : s1 / (double)h;
     a.hm[nd + i] = konst ? x0 : s2 / (double)h;
 }
@@ -100,12 +103,13 @@ __global__ __launch_bounds__(256) void mcalf_chain_centred_kernel(const ChainArg
     if (i >= nd) return;
     const int k = (int)(i % (size_t)a.d);
     const int64_t T = a.T, h = T / 2;
-    const double mu = a.mu[i], mean = a.pool[(size_t)k * kChainPool + kPoolMean], m1 = a.hm[i], m2 = a.hm[nd + i];
+    const double dl = a.kf[i] != 0.0 ? 0.0 : a.mu[i], mean = a.pool[(size_t)k * kChainPool + kPoolMean], m1 = a.hm[i], m2 = a.hm[nd + i];
     const double* x = a.X + i;
+    const double x0 = x[0];
     double c0 = 0.0, sq = 0.0, v1 = 0.0, v2 = 0.0;
     for (int64_t t = 0; t < T; ++t) {
         const double v = x[(size_t)t * nd];
-        const double xc = v - mu, dm = v - mean;
+        const double xc = (v - x0) - dl, dm = v - mean;
         c0 = __builtin_fma(xc, xc, c0);
         sq += dm * dm;
         if (t < h) { const double e = v - m1; v1 += e * e; }
@@ -149,19 +153,20 @@ __global__ __launch_bounds__(kChainBlock) void mcalf_chain_lag_kernel(const Chai
     for (int64_t w = w0; w < w1; ++w) {
         if (!chain_used(a, w)) continue;                                  // (uniform over the workgroup)
         const size_t wk = (size_t)w * a.d + k0;
-        const double smu = skv ? a.mu[wk + sc] : 0.0;
+        const double smu = skv && a.kf[wk + sc] == 0.0 ? a.mu[wk + sc] : 0.0;   // delta_w; a constant series is all 0
         const double* xw = a.X + wk + sc;
+        const double sx0 = skv ? xw[0] : 0.0;
         double c[kChainR];
 #pragma unroll
         for (int r = 0; r < kChainR; ++r) c[r] = 0.0;
         for (int64_t t0 = 0; t0 < T - tau0; t0 += kChainTB) {
             for (int i = si; i < kChainTB; i += kChainBlock / kChainKT) {
                 const int64_t t = t0 + i;
-                xa[sc * kChainTB + i] = skv && t < T ? xw[(size_t)t * nd] - smu : 0.0;
+                xa[sc * kChainTB + i] = skv && t < T ? (xw[(size_t)t * nd] - sx0) - smu : 0.0;
             }
             for (int i = si; i < kChainBLog; i += kChainBlock / kChainKT) {
                 const int64_t t = t0 + tau0 + i;
-                xb[sc * kChainBRow + i + i / kChainR] = skv && t < T ? xw[(size_t)t * nd] - smu : 0.0;
+                xb[sc * kChainBRow + i + i / kChainR] = skv && t < T ? (xw[(size_t)t * nd] - sx0) - smu : 0.0;
             }
             __syncthreads();
             if (mine) {
